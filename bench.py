@@ -28,6 +28,18 @@ Timing: W untimed warm-up steps, then exactly K steps bracketed by a barrier
 region every sweep-kernel launch is bracketed by its own HIP event pair on the
 stream it runs on (libpdd's event pool, no host syncs); roofline.achieved =
 algorithmic adds of those launches / their summed duration.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line: the headline figure and what the timed
+steps' own event pairs give.  `--full` adds the legs that are runs of their
+own after the timed steps: the CPU baselines (`cpu_baseline`), the PCIe-
+inclusive legs (`end_to_end_pcie`), the stream's pinned H2D rate and the
+subband per-stage roofline; without it those keys are null or absent.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs:
+float32 .npy, under 64 MB in all, larger planes as a fixed seeded sample) in
+every --config, once the timers are read; --rehearse refuses it; the
+inputs are seeded, so two builds run with the same arguments can be compared
+array for array.
 """
 import argparse
 import json
@@ -109,6 +121,50 @@ def synth_block(C, N, seed, dtype, device, rows_per_chunk=1 << 26):
         out[r:r + x.shape[0]] = x.to(out.dtype)
         del x
     return out
+
+
+# --dump-outputs: bytes of array data in all (every rank, every array); with the
+# .npy headers the files stay under 64 MB (64e6)
+DUMP_BUDGET = 60 * 10 ** 6
+
+
+def dump_outputs(dirpath, named, world=1, rank=0, seed=0):
+    """--dump-outputs DIR: the arrays the timed path returned in its last
+    step, as DIR/<name>.npy (float32; float64 stays float64), DUMP_BUDGET
+    bytes in all.  An array above its share of the budget is sampled the
+    same way every run: a 2-D plane keeps every row at a sorted, seeded
+    choice of columns (the first and the last among them), anything else a
+    sorted, seeded choice of flat elements.  The sample depends on the
+    array's shape and its position in ``named`` only, so two builds run
+    with the same arguments write the same elements.  At N > 1 every rank
+    writes its own arrays (<name>_rank<r>.npy)."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_BUDGET // max(1, len(named) * world)
+    for i, (name, t) in enumerate(named):
+        t = t.detach()
+        keep = share // (8 if t.dtype == torch.float64 else 4)
+        rng = np.random.default_rng([seed, i])
+        if t.numel() > keep and t.dim() == 2 and 2 * t.shape[0] <= keep:
+            ncol = keep // t.shape[0]
+            idx = rng.choice(t.shape[1] - 2, ncol - 2, replace=False) + 1
+            idx = np.sort(np.concatenate([[0, t.shape[1] - 1], idx]))
+            t = t.index_select(1, torch.from_numpy(idx).to(t.device))
+        elif t.numel() > keep:
+            idx = np.sort(rng.choice(t.numel(), keep, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        if t.dtype != torch.float64:
+            t = t.to(torch.float32)
+        if world > 1:
+            name = "%s_rank%d" % (name, rank)
+        np.save(os.path.join(dirpath, name + ".npy"), t.cpu().numpy())
+    log("rank %d: wrote %d output array(s) to %s" % (rank, len(named), dirpath))
+
+
+def _named(out, name="plane"):
+    """(name, tensor) pairs of what a step returned: one plane or a list."""
+    if torch.is_tensor(out):
+        return [(name, out)]
+    return [("%s_%d" % (name, k), p) for k, p in enumerate(out)]
 
 
 def cpu_baseline(C, n, dms, ntrials, dt, full_N):
@@ -359,6 +415,15 @@ def main():
     ap.add_argument("--zdm", default="auto", choices=["auto", "int", "wrap", "float", "none"],
                     help="stream: zero-DM mode (auto = 'wrap', the reference's uint8 result of "
                          "zero_dm_filter.py:30-39, on the exact 16-bit path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure, each a run of its own "
+                         "after the timed steps: the CPU baselines, the PCIe-inclusive legs, the "
+                         "stream's pinned H2D rate and the subband per-stage roofline (--no-e2e / "
+                         "--no-cpu-baseline drop one of them again)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned as "
+                         "DIR/<name>.npy (float32, at most 64 MB in all: larger arrays as a "
+                         "fixed, seeded sample; see dump_outputs)")
     ap.add_argument("--cpu-trials", type=int, default=None)
     ap.add_argument("--factor", default="auto", choices=["auto", "off", "2", "4", "force2", "force4"],
                     help="8-bit sweeps: exact factorisation over channel groups (auto = the "
@@ -368,10 +433,11 @@ def main():
     ap.add_argument("--no-skew", action="store_true",
                     help="factorised sweeps: plane-aligned tiles instead of delay-aligned ones "
                          "(the A/B of DESIGN.md §3.2; the plane is identical)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline legs")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="dmshard / timeshard: skip the PCIe-inclusive (pinned host -> H2D -> "
-                         "step) leg")
+                    help="--full (dmshard / timeshard) and --rehearse: skip the PCIe-inclusive "
+                         "(pinned host -> H2D -> step) leg")
     ap.add_argument("--e2e", action="store_true",
                     help="also time one PCIe-inclusive step: pinned host block -> H2D -> "
                          "sweep -> D2H of the plane into pinned host memory")
@@ -382,6 +448,11 @@ def main():
                          "slice's corner turn + its DM slice) and report per-rank times and the "
                          "predicted compute efficiency")
     args = ap.parse_args()
+    if args.dump_outputs and args.rehearse:
+        ap.error("--dump-outputs: a rehearsal (--rehearse) times each rank's step in turn and "
+                 "has no single step output to write")
+    if args.dump_outputs and args.steps is not None and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step")
     _maybe_spawn(args)
     if args.no_skew:
         from pypulsar_amd import sweep as _sweep_mod
@@ -496,8 +567,9 @@ def sweep_bench(args, cfg, rank, world, dev):
         sw.set_timing(True)  # event pair per sweep launch, no host syncs
     log("rank %d: timing %d steps" % (rank, steps))
     t0 = time.perf_counter()
+    out = None
     for i in range(steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -505,8 +577,12 @@ def sweep_bench(args, cfg, rank, world, dev):
     kern_ms, launches = sw.timing_read() if sw is not None else (0.0, 0)
     if sw is not None:
         sw.set_timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, _named(out), world, rank)
+    del out
     e2e = None
-    if mode == "dmshard" and not args.no_e2e:
+    pcie_leg = args.full and not args.no_e2e
+    if mode == "dmshard" and pcie_leg:
         # PCIe-inclusive: this rank's slices of the block in
         # pinned host memory -> H2D -> the step; planes stay resident (the
         # consumer is the on-device search), so no plane D2H
@@ -557,7 +633,7 @@ def sweep_bench(args, cfg, rank, world, dev):
                        "consumer is the on-device search), so nothing returns over PCIe; at "
                        "N = 1 the H2D of time batch k+1 runs on a copy stream under batch k's "
                        "sweep, at N > 1 the whole slice is copied before the step"}
-    if mode == "timeshard" and not args.no_e2e:
+    if mode == "timeshard" and pcie_leg:
         # PCIe-inclusive: this rank's input spectra (its
         # columns + the max-delay overlap) in pinned host memory -> H2D in 4
         # chunks on a copy stream, the columns swept in 4 ranges as their
@@ -758,7 +834,7 @@ def sweep_bench(args, cfg, rank, world, dev):
         }
         if e2e is not None:
             line["end_to_end_pcie"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             del step
             if mode in ("dmshard", "timeshard"):
                 del part
@@ -1075,6 +1151,15 @@ def ops_bench(args, cfg, rank, world, dev):
         rows.append({"kernel": name, "reference": ref, "bytes": nbytes, "ms": ms,
                      "achieved_GBs": gbs, "frac_hbm": gbs / PEAK_HBM_GBS})
 
+    if args.dump_outputs:
+        # every kernel's output buffer as its last launch left it (smooth and
+        # shift_pad share o_cn with the corner turn: the last writer's)
+        dump_outputs(args.dump_outputs, [("shift_group_sum_1", o_ser),
+                                         ("shift_group_sum_64", o_sub),
+                                         ("downsample_u8", o_ds), ("zero_dm", o_zt),
+                                         ("zdm_downsample", o_zd), ("channel_stats", o_c),
+                                         ("smooth", o_cn)], world, rank)
+
     # BASELINE.json configs[0] through the drop-in API
     wC, wN, wdm = cfg["wf_C"], cfg["wf_N"], cfg["wf_dm"]
     wfreqs = band(wC)
@@ -1095,7 +1180,7 @@ def ops_bench(args, cfg, rank, world, dev):
         ms = (time.perf_counter() - t0) / args.steps * 1e3
         wf["padval_%s" % pad] = {"ms": ms, "n_out": int(ser.shape[-1])}
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import spectra_oracle as orc
         xh = w8.cpu().numpy().astype(np.float64)
         cpu = {}
@@ -1154,6 +1239,15 @@ def search_bench(args, cfg, rank, world, dev):
     if world > 1:
         el = max_over_ranks(el, dev)
     ms = ev[0].elapsed_time(ev[1]) / args.steps
+    if args.dump_outputs:
+        # candidates land in atomic order: sorted by (row, start, width) here
+        k = min(int(count.item()), cands.shape[0])
+        c = cands[:k].cpu().numpy()
+        c = c[np.lexsort((c[:, 2], c[:, 1], c[:, 0]))]
+        rec = np.concatenate([c[:, :3].astype(np.float64),
+                              c[:, 3:].copy().view(np.float32).astype(np.float64)], axis=1)
+        dump_outputs(args.dump_outputs, [("count", count.double()),
+                                         ("candidates", torch.from_numpy(rec))], world, rank)
     byts = 2 * D * n * 4
     achieved = byts / (ms * 1e-3) / 1e9
     line = {
@@ -1240,6 +1334,11 @@ def stream_bench(args, cfg, rank, world, dev):
     el = time.perf_counter() - t0
     k_ms, k_n = st.sweep.timing_read()
     st.sweep.set_timing(False, code=_lib.U16 if st.exact else _lib.F32)
+    if args.dump_outputs and args.search:   # the last block's candidate records, field by field
+        rec = np.stack([item[f].astype(np.float64) for f in item.dtype.names], axis=1)
+        dump_outputs(args.dump_outputs, [("candidates", torch.from_numpy(rec))], world, rank)
+    elif args.dump_outputs:                 # the last block's (t0, plane)
+        dump_outputs(args.dump_outputs, _named(item[1]), world, rank)
     if world > 1:
         el = max_over_ranks(el, dev)
     units = D * nb * C * args.steps * world
@@ -1250,15 +1349,15 @@ def stream_bench(args, cfg, rank, world, dev):
     fx_g, fx_pat = st.sweep.factor_info(2 if st.exact else 0) if st.exact else (0, 0)
     h2d_bytes = block * C  # one 8-bit block per step over PCIe (pinned, async)
     # the binding resource: the block's pinned H2D, against this box's own
-    # pinned H2D rate (the same bytes copied alone, best of 5)
-    h2d_peak = _pinned_h2d_GBs(chunks[0], dev)
+    # pinned H2D rate (the same bytes copied alone, best of 5: --full)
+    h2d_peak = _pinned_h2d_GBs(chunks[0], dev) if args.full else None
     h2d_at = h2d_bytes / (ms * 1e-3) / 1e9
     # the sweep kernel alone: factorised adds per launch over its HIP-event time
     k_adds = D * nb * C / max(1, fx_g)
     k_launch_ms = k_ms / k_n if k_n else None
     k_tadds = k_adds / (k_launch_ms * 1e-3) / 1e12 if k_launch_ms else None
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = stream_cpu_baseline(C, ds, dms, dt, nb, D, st.mode)
     line = {
         "metric": "DM-trial samples*channels/sec (node) + % HBM roofline",
@@ -1352,8 +1451,9 @@ def subband_bench(args, cfg, rank, world, dev):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        one()
+        out = one()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -1361,7 +1461,10 @@ def subband_bench(args, cfg, rank, world, dev):
     if world > 1:
         el = max_over_ranks(el, dev)
     ms = el / args.steps * 1e3
-    roof = subband_roofline(ex, s, one, args.steps, C, N) if world == 1 else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, _named([p for _, _, p in out]), world, rank)
+    del out
+    roof = subband_roofline(ex, s, one, args.steps, C, N) if world == 1 and args.full else None
     line = {
         "metric": "DM-trial samples*channels/sec (node) + % HBM roofline",
         "value": units * args.steps * world / el,

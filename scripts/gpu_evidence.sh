@@ -22,7 +22,7 @@ tests)
   timeout -k 10 900 python -u -m pytest ${TFILES:-tests} -m gpu -q -x --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { echo PYTEST_FAIL; tail -30 $O/pytest_gpu.log; exit 1; }
   tail -1 $O/pytest_gpu.log ;;
 bench)
-  IFS=';' read -ra L <<< "${BENCH:-config3|;northstar|--config northstar --no-cpu-baseline --no-e2e}"
+  IFS=';' read -ra L <<< "${BENCH:-config3|--full;northstar|--config northstar --no-cpu-baseline --no-e2e}"
   for item in "${L[@]}"; do
     name=${item%%|*}; args=${item#*|}
     run ${BT:-600} bench_$name python bench.py $args
