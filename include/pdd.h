@@ -361,6 +361,51 @@ int pdd_sp_search(const float* x, int64_t D, int64_t n, int64_t ld, int64_t L, c
                   const int32_t* widths, int n_widths, float threshold, int32_t* cands,
                   int64_t max_cands, unsigned long long* count, void* stream);
 
+/* ---- periodicity search of a DM-time plane (pypulsar_amd/periodicity.py;
+ * the arithmetic of PrestoFFT.deredden, formats/prestofft.py:151-195, and
+ * PrestoFFT.harmonic_sum, :98-113).  Spectra are interleaved (re, im)
+ * float32 pairs with row stride ld in COMPLEX elements; nn = nfft / 2 bins of
+ * a row are used (no Nyquist bin).  offs, lens: DEVICE int32 tables of the B
+ * whitening blocks (periodicity.deredden_table; lens <= 256). */
+/* out[d][t] = float32(double(x[d][t]) - mean_d) for t < n, 0 for
+ * n <= t < nfft (out: [D][nfft], contiguous); mean_d accumulated in float64
+ * in a fixed order (deterministic).  Zero padding after mean removal stands
+ * in for PRESTO's pad-with-mean. */
+int pdd_ps_prep(const float* x, int64_t D, int64_t n, int64_t ld, int64_t nfft, float* out,
+                void* stream);
+/* med[d][j] = median(P[offs[j] : offs[j] + lens[j]]) / ln 2, P = re*re + im*im
+ * in float32; np.median's rule (even length: mean of the two middle values),
+ * by exact selection.  med: [D][B]. */
+int pdd_ps_block_medians(const float* spec, int64_t D, int64_t nn, int64_t ld, const int32_t* offs,
+                         const int32_t* lens, int64_t B, float* med, void* stream);
+/* The reference's whitening applied to powers: for block j < B - 1 and
+ * offset i in it, lineval = med[j] + slope_j (0.5 (lens[j] + lens[j+1]) - i),
+ * slope_j = (med[j+1] - med[j]) / (lens[j] + lens[j+1]); from offs[B-1] to nn
+ * the last lineval of block B - 2.  powers_out[d][k] = P / lineval
+ * ([D][nn], contiguous; bin 0 is 1); spec_out (may be null): the complex
+ * spectrum times 1 / sqrt(lineval) ([D][nn] complex, contiguous; bin 0 is
+ * 1 + 0j) -- the reference's return value.  Where lineval <= 0 or NaN (a
+ * dead row) both are 0 (the reference gives inf / NaN).  B >= 2. */
+int pdd_ps_normalise(const float* spec, int64_t D, int64_t nn, int64_t ld, const int32_t* offs,
+                     const int32_t* lens, int64_t B, const float* med, float* powers_out,
+                     float* spec_out, void* stream);
+/* out[d][k] = sum_{h=1..nharm} powers[d][h k] for k < nn / nharm
+ * (out: [D][nn / nharm], contiguous), float32, ascending h (numpy's += order:
+ * bit-identical to the reference for equal input).  nharm 1..32. */
+int pdd_ps_harmsum(const float* powers, int64_t D, int64_t nn, int64_t ld, int nharm, float* out,
+                   void* stream);
+/* All stages fused (harms: HOST array, ascending, 1..32, at most 8; thr: HOST
+ * array, one float threshold per stage): the sums run cumulatively in
+ * ascending h, so each stage's sum has the bits of pdd_ps_harmsum.  Bin k of
+ * [rlo, nn / H) is a candidate of stage H when S_H[k] >= thr, S_H[k] >
+ * S_H[k-1] and S_H[k] >= S_H[k+1] (neighbours outside the range: -inf).
+ * Records int32 {row, k, H, float-bits S_H[k]} are appended through the
+ * device counter *count exactly as by pdd_sp_search (always incremented,
+ * stored while < max_cands: the caller checks for overflow). */
+int pdd_ps_search(const float* powers, int64_t D, int64_t nn, int64_t ld, const int32_t* harms,
+                  int n_harms, const float* thr, int64_t rlo, int32_t* cands, int64_t max_cands,
+                  unsigned long long* count, void* stream);
+
 /* ---- PSRFITS search-mode subints -> [nchan][N] float32 (SURVEY.md §8(f)
  * rank 3).  Replaces psrfits.unpack_4bit (formats/psrfits.py:37-50),
  * PsrfitsFile.read_subint (:67-107: ((data*scales)+offsets)*weights in

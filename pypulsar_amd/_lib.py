@@ -50,7 +50,8 @@ EXPORTS = (
     "pdd_sweep_plan_create_ex", "pdd_sweep_plan_factor", "pdd_sweep_plan_skew", "pdd_source_digest",
     "pdd_sweep_plan_set_poison", "pdd_sweep_plan_set_segment_bytes",
     "pdd_sweep_pattern_bytes", "pdd_sweep_execute_stage", "pdd_stream_create_cu_mask",
-    "pdd_stream_destroy",
+    "pdd_stream_destroy", "pdd_ps_prep", "pdd_ps_block_medians", "pdd_ps_normalise",
+    "pdd_ps_harmsum", "pdd_ps_search",
 )
 
 
@@ -126,6 +127,11 @@ _SIGS = {
                        _vp, _int, ctypes.c_float, _vp, _i64, _vp, _vp], _int),
     "pdd_psrfits_subints": ([_vp, _i64, _i64, _i64, _int, _i64, _i64, _vp, _i64, _i64, _int, _vp,
                              _i64, _vp], _int),
+    "pdd_ps_prep": ([_vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
+    "pdd_ps_block_medians": ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp], _int),
+    "pdd_ps_normalise": ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _int),
+    "pdd_ps_harmsum": ([_vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
+    "pdd_ps_search": ([_vp, _i64, _i64, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp], _int),
 }
 
 
