@@ -406,6 +406,44 @@ int pdd_ps_search(const float* powers, int64_t D, int64_t nn, int64_t ld, const 
                   int n_harms, const float* thr, int64_t rlo, int32_t* cands, int64_t max_cands,
                   unsigned long long* count, void* stream);
 
+/* ---- folding of plane rows at candidate periods and the search of the folds
+ * over period / period-derivative offsets (pypulsar_amd/fold.py; restated in
+ * tests/fold_oracle.py).  Phase is a 64-bit unsigned fraction of a turn with
+ * wrap-around arithmetic.  A job is 4 int64 {row, P0, step, accel} (the last
+ * three the bit patterns of unsigned values, fold.phase_steps):
+ *   step  = round(f dt 2^64) mod 2^64,  accel = round(fd dt dt 2^64) mod 2^64,
+ *   P0    = round(phi0 2^64) + step / 2 (the centre of sample 0).
+ * Sample i of the row has P_i = P0 + i step + (i (i - 1) / 2) accel (mod
+ * 2^64) and falls into bin ((P_i >> 32) * nbins) >> 32. */
+/* The row is cut into npart parts of L = n / npart samples (the last
+ * n - npart L samples are not folded).  Per job: prof[J][npart][nbins]
+ * float64 sums of the samples per bin, cnt[J][npart][nbins] int32 sample
+ * counts, sumsq[J][npart] float64 sums of squares.  Accumulation is float64
+ * in no fixed order: exact (bit-identical to any order) on integer-valued
+ * rows.  jobs: HOST copy, jobs_dev: the same J x 4 int64 on the device; a
+ * row outside [0, D) is refused before anything is launched.  2 <= nbins <=
+ * 256, 1 <= npart <= 128, npart nbins <= 8192, n < 2^31; J == 0: no-op. */
+int pdd_fold_rows(const float* plane, int64_t D, int64_t n, int64_t ld, const int64_t* jobs,
+                  const int64_t* jobs_dev, int64_t J, int npart, int nbins, double* prof,
+                  int32_t* cnt, double* sumsq, void* stream);
+/* For each job and every trial (ia, ib) of [-A, A] x [-B, B]: with N = npart
+ * and m = 2 p + 1 - N, part p is shifted by
+ *   s_p = floor((ia m N + 2 ib m m + N N) / (2 N N))      (floor division)
+ * bins, the nearest bin to ia u + 4 ib u u, u = m / (2 N):
+ *   S[b] = sum_p prof[p][(b + s_p) mod nbins] (ascending p), C[b] from cnt,
+ *   chi2[ia][ib] = (sum over b ascending, C[b] > 0, of
+ *                   (S[b] - C[b] mu)^2 / (C[b] var)) / (nbins - 1),
+ * all float64 without contraction.  mu = tot / Ntot and var = q / Ntot - mu mu
+ * with tot the sum over ascending p of (the sum over ascending b of
+ * prof[p][b]), q the sum of sumsq over ascending p, Ntot the sample count;
+ * var <= 0 gives chi2 = 0.  chi2: [J][2A+1][2B+1].  best[J][2] = (ia, ib) of
+ * the first trial in the order (chi2 descending, |ib|, |ia|, ib, ia
+ * ascending), best_chi2[J] its chi2, best_prof[J][nbins] / best_cnt[J][nbins]
+ * its S and C.  A, B <= 256. */
+int pdd_fold_search(const double* prof, const int32_t* cnt, const double* sumsq, int64_t J,
+                    int npart, int nbins, int A, int B, double* chi2, int32_t* best,
+                    double* best_chi2, double* best_prof, int32_t* best_cnt, void* stream);
+
 /* ---- PSRFITS search-mode subints -> [nchan][N] float32 (SURVEY.md §8(f)
  * rank 3).  Replaces psrfits.unpack_4bit (formats/psrfits.py:37-50),
  * PsrfitsFile.read_subint (:67-107: ((data*scales)+offsets)*weights in

@@ -51,7 +51,7 @@ EXPORTS = (
     "pdd_sweep_plan_set_poison", "pdd_sweep_plan_set_segment_bytes",
     "pdd_sweep_pattern_bytes", "pdd_sweep_execute_stage", "pdd_stream_create_cu_mask",
     "pdd_stream_destroy", "pdd_ps_prep", "pdd_ps_block_medians", "pdd_ps_normalise",
-    "pdd_ps_harmsum", "pdd_ps_search",
+    "pdd_ps_harmsum", "pdd_ps_search", "pdd_fold_rows", "pdd_fold_search",
 )
 
 
@@ -132,6 +132,10 @@ _SIGS = {
     "pdd_ps_normalise": ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _int),
     "pdd_ps_harmsum": ([_vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
     "pdd_ps_search": ([_vp, _i64, _i64, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp], _int),
+    "pdd_fold_rows": ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp],
+                      _int),
+    "pdd_fold_search": ([_vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp,
+                         _vp], _int),
 }
 
 

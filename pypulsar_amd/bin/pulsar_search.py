@@ -11,10 +11,14 @@ power spectrum is whitened (PrestoFFT.deredden, prestofft.py:151-195),
 harmonic summed (PrestoFFT.harmonic_sum, :98-113) and searched
 (pypulsar_amd.periodicity) in batches of DM rows; only candidates come back to
 the host.  They are sifted across DMs and harmonics and written in the
-``.accelcands`` layout.
+``.accelcands`` layout.  With ``--fold K`` the K strongest sifted candidates
+are then folded on the plane (pypulsar_amd.fold: their own DM row and its
+neighbours, a search over period and period derivative) and written as
+``<base>_cand<k>.bestprof`` and ``<base>_cand<k>.npz``.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
 """
 import optparse
 import os
@@ -26,8 +30,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
-                nfft=None, row_batch=None):
-    """(candidate records, sample time of the searched plane)."""
+                nfft=None, row_batch=None, return_plane=False):
+    """(candidate records, sample time of the searched plane); with
+    ``return_plane`` also the searched [D, n] float32 device plane (for
+    pypulsar_amd.fold): (candidates, sample time, plane)."""
     import torch
     from pypulsar_amd.formats import filterbank
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
@@ -52,6 +58,8 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     ps = PeriodicitySearch(sigma, harms or DEFAULT_HARMS, flo=flo)
     cands = ps(plane, dms, dt, row_batch=row_batch, nfft=nfft)
     sw.close()
+    if return_plane:
+        return cands, dt, plane
     return cands, dt
 
 
@@ -76,6 +84,16 @@ def main(argv=None):
                       help="FFT length (even; default: next power of two).")
     parser.add_option("--row-batch", type="int", default=None,
                       help="DM rows searched at once (default: bounded by the workspace).")
+    parser.add_option("--fold", type="int", default=0,
+                      help="Fold the K strongest sifted candidates on the plane and refine "
+                           "period, period derivative and DM; writes <base>_cand<k>.bestprof "
+                           "and <base>_cand<k>.npz. (Default: 0, no folding)")
+    parser.add_option("--fold-nbins", dest="fold_nbins", type="int", default=64,
+                      help="Profile bins of a fold. (Default: 64)")
+    parser.add_option("--fold-npart", dest="fold_npart", type="int", default=32,
+                      help="Sub-integrations of a fold. (Default: 32)")
+    parser.add_option("--fold-dm-halfwidth", dest="fold_dm_halfwidth", type="int", default=2,
+                      help="DM trials folded on each side of a candidate's. (Default: 2)")
     parser.add_option("-o", "--outname", default=None,
                       help="Output .accelcands file (default: INFILE with .accelcands).")
     options, args = parser.parse_args(argv)
@@ -84,14 +102,38 @@ def main(argv=None):
     from pypulsar_amd.periodicity import sift, write_accelcands
     harms = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= options.numharm) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
-    cands, _ = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
-                           options.flo, options.nfft, options.row_batch)
+    res = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
+                      options.flo, options.nfft, options.row_batch,
+                      return_plane=options.fold > 0)
+    cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]
     out = options.outname or base + ".accelcands"
     write_accelcands(sifted, out, basename=os.path.basename(base))
     print("%d candidates (%d sifted) -> %s" % (len(cands), len(sifted), out))
+    if options.fold > 0:
+        fold_candidates(res[2], dms, res[1], sifted[:options.fold], os.path.splitext(out)[0],
+                        args[0], options.fold_npart, options.fold_nbins,
+                        options.fold_dm_halfwidth)
     return 0
+
+
+def fold_candidates(plane, dms, dt, sifted, base, infile, npart=32, nbins=64, dm_halfwidth=2):
+    """Fold sifted candidates on the plane; writes ``<base>_cand<k>.bestprof``
+    and ``<base>_cand<k>.npz`` (k from 1, by descending sigma) and prints one
+    line per candidate.  Returns the FoldedCandidates."""
+    from pypulsar_amd.fold import Folder, write_bestprof
+    folded = Folder(npart, nbins)(plane, dms, dt, sifted, dm_halfwidth=dm_halfwidth)
+    for k, fc in enumerate(folded, 1):
+        name = "%s_cand%d" % (base, k)
+        write_bestprof(fc, name + ".bestprof", infile=infile, candname=os.path.basename(name))
+        np.savez(name + ".npz", subints=fc.subints, subint_counts=fc.subint_counts,
+                 chi2_plane=fc.chi2_plane, chi2_vs_dm=fc.chi2_vs_dm, dms=fc.dms,
+                 profile=fc.profile, counts=fc.counts, trial=np.asarray(fc.trial),
+                 f=fc.f, fd=fc.fd, dm=fc.dm, chi2=fc.chi2, sigma=fc.sigma)
+        print("cand %d: DM %.2f  P %.9f ms  fd %.3g Hz/s  reduced chi2 %.2f  sigma %.1f -> %s" % (
+            k, fc.dm, 1000.0 * fc.period, fc.fd, fc.chi2, fc.sigma, name + ".bestprof"))
+    return folded
 
 
 if __name__ == "__main__":

@@ -13,4 +13,5 @@ rm -rf build/dev_src && mkdir -p build/dev_src/pypulsar_amd && cp -r pypulsar_am
 S=build/dev_src/pypulsar_amd/csrc
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -fno-slp-vectorize \
   -ffp-contract=off -DPDD_SWEEP_DEV ${DEV_FLAGS:-} -I include -o ${DEV_OUT:-build/libpdd_dev.so} \
-  $S/pdd_ops.hip $S/pdd_sweep.hip $S/pdd_search.hip $S/pdd_psrfits.hip
+  $S/pdd_ops.hip $S/pdd_sweep.hip $S/pdd_search.hip $S/pdd_psrfits.hip $S/pdd_period.hip \
+  $S/pdd_fold.hip

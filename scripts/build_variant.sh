@@ -10,4 +10,4 @@ mkdir -p build
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -fno-slp-vectorize \
   -ffp-contract=off "$@" -o build/libpdd_$name.so \
   pypulsar_amd/csrc/pdd_ops.hip pypulsar_amd/csrc/pdd_sweep.hip pypulsar_amd/csrc/pdd_search.hip \
-  pypulsar_amd/csrc/pdd_psrfits.hip
+  pypulsar_amd/csrc/pdd_psrfits.hip pypulsar_amd/csrc/pdd_period.hip pypulsar_amd/csrc/pdd_fold.hip
