@@ -406,6 +406,38 @@ int pdd_ps_search(const float* powers, int64_t D, int64_t nn, int64_t ld, const 
                   int n_harms, const float* thr, int64_t rlo, int32_t* cands, int64_t max_cands,
                   unsigned long long* count, void* stream);
 
+/* ---- acceleration search in the Fourier domain (pypulsar_amd/accel.py;
+ * PrestoFFT.interpolate, formats/prestofft.py:76-96, carried to drifting
+ * signals).  spec: the whitened complex spectrum of pdd_ps_normalise,
+ * interleaved (re, im) float32, row stride ld in COMPLEX elements, nn bins a
+ * row; bins outside [0, nn) count as 0. */
+/* powers[d][j][i] = |sum_{e=-hw[j]..hw[j]} F[d][k0 + e] t[j][phi][e]|^2 with
+ * k0 = i >> 1, phi = i & 1, i < 2 nn (half-bin positions).  taps: DEVICE
+ * float32 [nz][2][2 M + 1][2] = (re, im) of t[j][phi][e] at index M + e
+ * (accel.template_bank); hw: HOST int32 [nz], 0 <= hw[j] <= M <= 512 (z values
+ * are processed four at a time to the largest half-width of the four, so
+ * taps beyond hw[j] must be 0); nz odd, <= 255.  powers: [D][nz][2 nn]
+ * float32, contiguous.  float32 fused multiply-adds in a fixed order
+ * (deterministic). */
+int pdd_acc_correlate(const float* spec, int64_t D, int64_t nn, int64_t ld, const float* taps,
+                      const int32_t* hw, int nz, int M, float* powers, void* stream);
+/* Harmonic stages on the TOP harmonic's grid and the candidate search of
+ * powers [D][nz][ni] (contiguous; J0 = (nz - 1) / 2, jc = j - J0).  harms:
+ * HOST array, ascending, 1..16, at most 8; thr: HOST array, one float
+ * threshold per stage.
+ *   S_H[jc][i] = sum_{h=1..H} P[J0 + floor((jc h + H / 2) / H)][(i h + H / 2) / H]
+ * (float32, ascending h from the h = 1 term; H / 2 an integer division).
+ * Cell (j, i) with i >= 2 H rlo is a candidate of stage H when S >= thr, S >
+ * its neighbours (j-1, i-1), (j-1, i), (j-1, i+1), (j, i-1) and S >= the
+ * neighbours (j, i+1), (j+1, i-1), (j+1, i), (j+1, i+1); neighbours outside
+ * [0, nz) x [2 H rlo, ni) count as -inf.  Records int32 {row, i, jc, H,
+ * float-bits S, 0} are appended through the device counter *count exactly as
+ * by pdd_ps_search (always incremented, stored while < max_cands: the caller
+ * checks for overflow). */
+int pdd_acc_search(const float* powers, int64_t D, int nz, int64_t ni, const int32_t* harms,
+                   int n_harms, const float* thr, int64_t rlo, int32_t* cands, int64_t max_cands,
+                   unsigned long long* count, void* stream);
+
 /* ---- folding of plane rows at candidate periods and the search of the folds
  * over period / period-derivative offsets (pypulsar_amd/fold.py; restated in
  * tests/fold_oracle.py).  Phase is a 64-bit unsigned fraction of a turn with

@@ -14,11 +14,15 @@ the host.  They are sifted across DMs and harmonics and written in the
 ``.accelcands`` layout.  With ``--fold K`` the K strongest sifted candidates
 are then folded on the plane (pypulsar_amd.fold: their own DM row and its
 neighbours, a search over period and period derivative) and written as
-``<base>_cand<k>.bestprof`` and ``<base>_cand<k>.npz``.
+``<base>_cand<k>.bestprof`` and ``<base>_cand<k>.npz``.  With ``--zmax Z`` the
+rows are searched for signals that drift up to Z Fourier bins over the
+observation (pulsars in binaries; pypulsar_amd.accel): the candidates carry
+their ``z``, and a fold starts from their frequency derivative.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
 """
 import optparse
 import os
@@ -30,10 +34,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
-                nfft=None, row_batch=None, return_plane=False):
+                nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
-    pypulsar_amd.fold): (candidates, sample time, plane)."""
+    pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
+    acceleration search (pypulsar_amd.accel.AccelSearch, records of
+    ACCEL_CAND_DTYPE) on a z grid of ``dz``; ``harms`` then at most 16."""
     import torch
     from pypulsar_amd.formats import filterbank
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
@@ -55,7 +61,11 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     sw = DMSweep(dms, fb.freqs, dt, dtype="f32")
     plane = sw(img, trim=True)
     del img
-    ps = PeriodicitySearch(sigma, harms or DEFAULT_HARMS, flo=flo)
+    if zmax > 0:
+        from pypulsar_amd.accel import DEFAULT_HARMS as ACCEL_HARMS, AccelSearch
+        ps = AccelSearch(sigma, zmax, dz, harms or ACCEL_HARMS, flo=flo)
+    else:
+        ps = PeriodicitySearch(sigma, harms or DEFAULT_HARMS, flo=flo)
     cands = ps(plane, dms, dt, row_batch=row_batch, nfft=nfft)
     sw.close()
     if return_plane:
@@ -84,6 +94,12 @@ def main(argv=None):
                       help="FFT length (even; default: next power of two).")
     parser.add_option("--row-batch", type="int", default=None,
                       help="DM rows searched at once (default: bounded by the workspace).")
+    parser.add_option("--zmax", type="int", default=0,
+                      help="Largest searched drift in Fourier bins over the observation "
+                           "(z = fd T^2): the acceleration search; caps --numharm at 16. "
+                           "(Default: 0, the periodicity search)")
+    parser.add_option("--dz", type="int", default=2,
+                      help="Step of the z grid of the acceleration search. (Default: 2)")
     parser.add_option("--fold", type="int", default=0,
                       help="Fold the K strongest sifted candidates on the plane and refine "
                            "period, period derivative and DM; writes <base>_cand<k>.bestprof "
@@ -100,16 +116,19 @@ def main(argv=None):
     if len(args) != 1:
         parser.error("one input filterbank expected")
     from pypulsar_amd.periodicity import sift, write_accelcands
-    harms = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= options.numharm) or (1,)
+    if options.zmax < 0 or options.dz < 1:
+        parser.error("--zmax must be >= 0 and --dz >= 1")
+    numharm = min(options.numharm, 16) if options.zmax > 0 else options.numharm
+    harms = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= numharm) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
     res = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
                       options.flo, options.nfft, options.row_batch,
-                      return_plane=options.fold > 0)
+                      return_plane=options.fold > 0, zmax=options.zmax, dz=options.dz)
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]
     out = options.outname or base + ".accelcands"
-    write_accelcands(sifted, out, basename=os.path.basename(base))
+    write_accelcands(sifted, out, basename=os.path.basename(base), zmax=options.zmax)
     print("%d candidates (%d sifted) -> %s" % (len(cands), len(sifted), out))
     if options.fold > 0:
         fold_candidates(res[2], dms, res[1], sifted[:options.fold], os.path.splitext(out)[0],

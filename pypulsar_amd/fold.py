@@ -212,7 +212,11 @@ class Folder(object):
         frequency on its own row and ``dm_halfwidth`` rows on each side
         (clipped at the plane's edges), all folds of the call in one
         pdd_fold_rows and one pdd_fold_search; the row with the largest best
-        chi-square wins (ties: the candidate's own row).  Returns a list of
+        chi-square wins (ties: the candidate's own row).  A candidate that
+        carries ``fd != 0`` (one of the acceleration search, whose frequency
+        is the mid-observation one) is folded at ``(f - fd n dt / 2, fd)``,
+        the frequency at the first sample, and refined from there; a pair
+        may be a triple ``(row, freq, fd)``.  Returns a list of
         FoldedCandidate."""
         dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
         D, n = plane.shape
@@ -222,22 +226,27 @@ class Folder(object):
         want = []
         for c in cands:
             row, f = (int(c.row), float(c.freq)) if hasattr(c, "freq") else (int(c[0]), float(c[1]))
+            fd = float(getattr(c, "fd", 0.0)) if hasattr(c, "freq") else \
+                (float(c[2]) if len(c) > 2 else 0.0)
+            if fd != 0.0:
+                f = f - 0.5 * fd * n * float(dt)
             if row < 0 and hasattr(c, "dm") and D:
                 # (a candidate read back from a .accelcands file: the nearest DM trial)
                 row = int(np.argmin(np.abs(dms - float(c.dm))))
             if not 0 <= row < D:
                 raise ValueError("candidate row %d outside the plane's %d rows" % (row, D))
-            want.append((row, f, list(range(max(0, row - h), min(D, row + h + 1)))))
+            want.append((row, f, list(range(max(0, row - h), min(D, row + h + 1))), fd))
         if not want:
             return []
         rows = np.concatenate([w[2] for w in want])
         freqs = np.concatenate([[w[1]] * len(w[2]) for w in want])
-        prof, cnt, sumsq = self.fold(plane, rows, freqs, 0.0, dt)
+        fds = np.concatenate([[w[3]] * len(w[2]) for w in want])
+        prof, cnt, sumsq = self.fold(plane, rows, freqs, fds, dt)
         chi2, best, best_chi2, best_prof, best_cnt = self.search(prof, cnt, sumsq)
         best, best_chi2 = best.cpu().numpy(), best_chi2.cpu().numpy()
         T = self.span(n, dt)
         out, j0 = [], 0
-        for row, f, rr in want:
+        for row, f, rr, fd in want:
             cv = best_chi2[j0:j0 + len(rr)]
             k = rr.index(row)
             for q in range(len(rr)):
@@ -245,7 +254,7 @@ class Folder(object):
                     k = q
             j = j0 + k
             ia, ib = int(best[j, 0]), int(best[j, 1])
-            f1, fd1 = trial_to_ffdot(ia, ib, f, 0.0, self.nbins, T)
+            f1, fd1 = trial_to_ffdot(ia, ib, f, fd, self.nbins, T)
             pj, cj = prof[j].cpu().numpy(), cnt[j].cpu().numpy()
             nsamp = int(cj.astype(np.int64).sum())
             avg = float(pj.sum() / nsamp) if nsamp else 0.0

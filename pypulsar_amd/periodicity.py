@@ -343,10 +343,16 @@ def merge(parts):
 
 class SiftedCandidate(object):
     """A candidate with its DM hits (the fields of a ``.accelcands`` entry).
-    ``hits``: [(DM, sigma)] sorted by DM, the candidate's own DM included."""
+    ``hits``: [(DM, sigma)] sorted by DM, the candidate's own DM included.
+    ``z``: the drift in Fourier bins over the observation and ``fd`` the
+    frequency derivative (Hz / s) of a candidate of the acceleration search
+    (pypulsar_amd.accel), whose ``period`` is the mid-observation one; both 0
+    otherwise."""
 
-    def __init__(self, dm, r, period, numharm, power, sigma, row=-1, accelfile=None, candnum=None):
+    def __init__(self, dm, r, period, numharm, power, sigma, row=-1, accelfile=None, candnum=None,
+                 z=0.0, fd=0.0):
         self.dm, self.r, self.period = float(dm), float(r), float(period)
+        self.z, self.fd = float(z), float(fd)
         self.numharm, self.power, self.sigma = int(numharm), float(power), float(sigma)
         self.row = int(row)
         self.accelfile, self.candnum = accelfile, candnum
@@ -367,10 +373,15 @@ def sift(cands, rtol_bins=1.5, max_ratio=16):
     whose ``r`` it matches within ``rtol_bins``, or of whose ``r`` it is --
     or which is of its ``r`` -- an integer multiple m <= max_ratio within
     ``rtol_bins``.  An absorbed candidate at another DM becomes a DM hit;
-    each DM keeps its best sigma.  Returns SiftedCandidates by descending
-    sigma."""
+    each DM keeps its best sigma.  Records of the acceleration search (with a
+    ``zbins`` field, the drift in bins of ``r``) match within ``rtol_bins +
+    0.5 |zbins_a - m zbins_b|``: the Fresnel sidelobes of one signal lie
+    within half the z difference in r.  Returns SiftedCandidates by
+    descending sigma."""
     order = np.argsort(-cands["sigma"], kind="stable")
     kept, kept_r = [], np.empty(0)
+    has_z = cands.dtype.names is not None and "zbins" in cands.dtype.names
+    kept_z = np.empty(0)
     m = np.arange(1, int(max_ratio) + 1, dtype=np.float64)
     for i in order:
         c = cands[i]
@@ -378,13 +389,21 @@ def sift(cands, rtol_bins=1.5, max_ratio=16):
         j = -1
         if len(kept):
             big, small = np.maximum(kept_r, r), np.minimum(kept_r, r)
-            rel = np.any(np.abs(big[:, None] - m[None, :] * small[:, None]) <= rtol_bins, axis=1)
+            tol = rtol_bins
+            if has_z:
+                zb = float(c["zbins"])
+                zbig, zsmall = np.where(kept_r >= r, kept_z, zb), np.where(kept_r >= r, zb, kept_z)
+                tol = rtol_bins + 0.5 * np.abs(zbig[:, None] - m[None, :] * zsmall[:, None])
+            rel = np.any(np.abs(big[:, None] - m[None, :] * small[:, None]) <= tol, axis=1)
             hit = np.flatnonzero(rel)
             if len(hit):
                 j = int(hit[0])
         if j < 0:
             s = SiftedCandidate(c["DM"], r, c["period"], c["numharm"], c["power"], c["sigma"],
                                 row=c["row"])
+            if has_z:
+                s.z, s.fd = float(c["z"]), float(c["fd"])
+                kept_z = np.append(kept_z, float(c["zbins"]))
             s._hits = {float(c["DM"]): float(c["sigma"])}
             kept.append(s)
             kept_r = np.append(kept_r, r)
@@ -403,23 +422,25 @@ ACCELCANDS_HEADER = ("#" + "file:candnum".center(66) + "DM".center(9) + "SNR".ce
                      "numhits".center(9) + "\n")
 
 
-def write_accelcands(sifted, fn, basename="pulsar_search"):
+def write_accelcands(sifted, fn, basename="pulsar_search", zmax=0):
     """Write SiftedCandidates in the ``.accelcands`` layout of
     formats/accelcands.py (``Candidate.__str__`` / ``DMHit.__str__``), by
     descending sigma, hits by ascending DM.  This search has no coherent
-    power, S/N or acceleration: ``ipow`` and ``cpow`` are both the summed
-    power, ``SNR`` is the sigma (also for the hits) and ``z`` is 0.
-    Candidates without a name are called ``<basename>_DM<dm>_ACCEL_0:<n>``."""
+    power or S/N: ``ipow`` and ``cpow`` are both the summed power, ``SNR`` is
+    the sigma (also for the hits); ``z`` is the candidate's (0 unless it comes
+    from the acceleration search).  Candidates without a name are called
+    ``<basename>_DM<dm>_ACCEL_<zmax>:<n>`` (``zmax``: the searched range, 0
+    for the periodicity search)."""
     cl = sorted(sifted, key=lambda c: -c.sigma)
     with open(fn, "w") as f:
         f.write(ACCELCANDS_HEADER)
         for n, c in enumerate(cl):
             name = c.accelfile if c.accelfile is not None \
-                else "%s_DM%.2f_ACCEL_0" % (basename, c.dm)
+                else "%s_DM%.2f_ACCEL_%d" % (basename, c.dm, int(zmax))
             cand = "%s:%d" % (name, c.candnum if c.candnum is not None else n + 1)
             f.write("%-65s   %7.2f  %6.2f  %6.2f  %s   %7.1f  %7.1f  %12.6f  %10.2f  %8.2f  (%d)\n"
                     % (cand, c.dm, c.sigma, c.sigma, "%2d".center(7) % c.numharm, c.power,
-                       c.power, c.period * 1000.0, c.r, 0.0, len(c.hits)))
+                       c.power, c.period * 1000.0, c.r, getattr(c, "z", 0.0) + 0.0, len(c.hits)))
             for dm, sg in sorted(c.hits):
                 f.write("  DM=%6.2f SNR=%5.2f Sigma=%5.2f" % (dm, sg, sg) +
                         "   " + int(sg / 3.0) * "*" + "\n")
@@ -442,9 +463,9 @@ def read_accelcands(fn):
         head, _, rest = line.rpartition("(")
         t = head.split()
         name, _, num = t[0].rpartition(":")
-        dm, _snr, sg, numharm, ipow, _cpow, pms, r, _z = t[1:10]
+        dm, _snr, sg, numharm, ipow, _cpow, pms, r, z = t[1:10]
         c = SiftedCandidate(dm, r, float(pms) / 1000.0, numharm, ipow, sg, accelfile=name,
-                            candnum=int(num))
+                            candnum=int(num), z=z)
         c._numhits = int(rest.split(")")[0])
         out.append(c)
     for c in out:
