@@ -476,6 +476,35 @@ int pdd_fold_search(const double* prof, const int32_t* cnt, const double* sumsq,
                     int npart, int nbins, int A, int B, double* chi2, int32_t* best,
                     double* best_chi2, double* best_prof, int32_t* best_cnt, void* stream);
 
+/* ---- RFI excision on the raw time-major block (pypulsar_amd/rfi.py; restated
+ * in tests/rfi_oracle.py).  raw: [nint ptsperint][C] 8-bit or float32 (dtype
+ * PDD_U8 / PDD_F32), row stride ld elements, cut into nint intervals of
+ * P = ptsperint samples (16 <= P <= 2^23). */
+/* Pass (a) over channels c0 .. c0 + nc - 1: avg[i][c] and std[i][c] (float64,
+ * [nint][C], only those columns written) of every (interval, channel) --
+ * 8 bits: from the exact integer sums S1 = sum x, S2 = sum x^2 as
+ * double(S1) / double(P) and sqrt(double(P S2 - S1 S1) / double(P P)); float32:
+ * from float64 sums -- and rows[(c - c0) nint + i][P] (float32, contiguous):
+ * the samples of the cell minus a constant near their mean (the mean of the
+ * first <= 64, rounded to an integer for 8 bits; bins k >= 1 of a transform
+ * of the row do not depend on it).  nvar[(c - c0) nint + i] = P var (float64). */
+int pdd_rfi_stats_prep(const void* raw, int dtype, int64_t nint, int64_t C, int64_t ld,
+                       int64_t ptsperint, int64_t c0, int64_t nc, float* rows, double* avg,
+                       double* std, double* nvar, void* stream);
+/* Pass (b): spec = the real-to-complex transform of `rows`, [nrows][P / 2 + 1]
+ * interleaved (re, im) float32, contiguous, 16-byte aligned; nrows = nc nint.
+ * pow[i][c0 + row / nint] (float64, [nint][C]) = max_{k=1..P/2} |spec[row][k]|^2
+ * / nvar[row], 0 where nvar[row] == 0; i = row % nint. */
+int pdd_rfi_stats_power(const float* spec, int64_t nrows, int64_t ptsperint, const double* nvar,
+                        int64_t nint, int64_t C, int64_t c0, double* pow, void* stream);
+/* In place on data [n][C] (row stride ld): sample (t, c) becomes fill[c] when
+ * bit c % 32 of bitmap[(t0 + t) / ptsperint][c / 32] is set (bitmap: uint32
+ * [nint][ceil(C / 32)], bits of channels >= C clear; fill: [C] of the data's
+ * type).  Rows of intervals >= nint are left alone. */
+int pdd_rfi_apply(void* data, int dtype, int64_t n, int64_t C, int64_t ld, int64_t t0,
+                  int64_t ptsperint, const uint32_t* bitmap, int64_t nint, const void* fill,
+                  void* stream);
+
 /* ---- PSRFITS search-mode subints -> [nchan][N] float32 (SURVEY.md §8(f)
  * rank 3).  Replaces psrfits.unpack_4bit (formats/psrfits.py:37-50),
  * PsrfitsFile.read_subint (:67-107: ((data*scales)+offsets)*weights in

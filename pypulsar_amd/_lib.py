@@ -52,7 +52,8 @@ EXPORTS = (
     "pdd_sweep_pattern_bytes", "pdd_sweep_execute_stage", "pdd_stream_create_cu_mask",
     "pdd_stream_destroy", "pdd_ps_prep", "pdd_ps_block_medians", "pdd_ps_normalise",
     "pdd_ps_harmsum", "pdd_ps_search", "pdd_fold_rows", "pdd_fold_search",
-    "pdd_acc_correlate", "pdd_acc_search",
+    "pdd_acc_correlate", "pdd_acc_search", "pdd_rfi_stats_prep", "pdd_rfi_stats_power",
+    "pdd_rfi_apply",
 )
 
 
@@ -139,6 +140,10 @@ _SIGS = {
                          _vp], _int),
     "pdd_acc_correlate": ([_vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp], _int),
     "pdd_acc_search": ([_vp, _i64, _int, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp], _int),
+    "pdd_rfi_stats_prep": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+                           _int),
+    "pdd_rfi_stats_power": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp], _int),
+    "pdd_rfi_apply": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp], _int),
 }
 
 

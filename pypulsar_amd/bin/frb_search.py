@@ -13,6 +13,12 @@ file's DM-time plane.  Output: PRESTO-style ``.singlepulse`` text.
 
     python -m pypulsar_amd.bin.frb_search --lodm 0 --hidm 1000 --numdms 2048 \\
         --downsamp 2 --threshold 7 -o obs.singlepulse obs.fil
+    python -m pypulsar_amd.bin.frb_search --rfifind 2.0 --numdms 2048 obs.fil
+    python -m pypulsar_amd.bin.frb_search --mask obs_rfifind.mask --numdms 2048 obs.fil
+
+``--mask`` / ``--rfifind``: the cells of an rfifind ``.mask`` (read, or made in
+a first pass over the file: pypulsar_amd.rfi) are replaced on the device by
+their channel's level before the zero-DM filter.
 """
 import optparse
 import os
@@ -43,8 +49,25 @@ def _chunks(fb, block, nbuf=4, start_block=0):
         i += 1
 
 
+def get_mask(infile, fb, maskfile=None, rfifind=None, block=1 << 18):
+    """The pypulsar_amd.rfi.RFIMask of a search: made in a first pass over the
+    file with intervals of ``rfifind`` seconds (and left beside it as
+    <base>_rfifind.mask), or read from ``maskfile``; None without either."""
+    if rfifind:
+        from pypulsar_amd.bin.rfifind import find_mask
+        mask = find_mask(infile, rfifind, block)
+        out = os.path.splitext(infile)[0] + "_rfifind.mask"
+        mask.write(out)
+        print("rfifind: %.2f%% masked -> %s" % (100.0 * mask.masked_fraction, out))
+        return mask
+    if maskfile:
+        from pypulsar_amd.rfi import mask_from_file
+        return mask_from_file(maskfile, fb, block)
+    return None
+
+
 def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=6.0,
-                widths=None, detrendlen=1024, debug=False):
+                widths=None, detrendlen=1024, debug=False, maskfile=None, rfifind=None):
     import torch
     from pypulsar_amd.formats import filterbank
     from pypulsar_amd.search import DEFAULT_WIDTHS, StreamingSearch, merge
@@ -55,7 +78,8 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
     tdt = torch.uint8 if np.dtype(fb.dtype) == np.uint8 else torch.float32
     ss = StreamingSearch(dms, fb.freqs, fb.tsamp, block=block, downsamp=downsamp,
                          zero_dm=zero_dm, dtype=tdt, threshold=threshold,
-                         widths=widths or DEFAULT_WIDTHS, detrendlen=detrendlen)
+                         widths=widths or DEFAULT_WIDTHS, detrendlen=detrendlen,
+                         rfimask=get_mask(infile, fb, maskfile, rfifind, block))
     parts = []  # candidate times are relative to the file start
     for i, c in enumerate(ss(_chunks(fb, block))):
         parts.append(c)
@@ -81,6 +105,13 @@ def main(argv=None):
                       help="Spectra per streamed block. (Default: 262144)")
     parser.add_option("--no-zero-dm", dest="zero_dm", action="store_false", default=True,
                       help="Skip the zero-DM filter.")
+    parser.add_option("--mask", dest="maskfile", type="string", default=None,
+                      help="rfifind .mask file: its cells are replaced by the channel's "
+                           "level before the zero-DM filter. (Default: no mask)")
+    parser.add_option("--rfifind", type="float", default=None, metavar="SECONDS",
+                      help="Make the mask in a first pass over the file, with intervals of "
+                           "SECONDS (written to <INFILE base>_rfifind.mask), then search "
+                           "with it.")
     parser.add_option("-t", "--threshold", type="float", default=6.0,
                       help="Candidate S/N threshold. (Default: 6)")
     parser.add_option("-m", "--maxwidth", type="int", default=150,
@@ -95,7 +126,8 @@ def main(argv=None):
     widths = tuple(w for w in DEFAULT_WIDTHS if w <= options.maxwidth) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
     cands = search_file(args[0], dms, options.downsamp, options.block, options.zero_dm,
-                        options.threshold, widths, debug=options.debug)
+                        options.threshold, widths, debug=options.debug,
+                        maskfile=options.maskfile, rfifind=options.rfifind)
     out = options.outname or os.path.splitext(args[0])[0] + ".singlepulse"
     write_singlepulse(cands, out)
     print("%d candidates -> %s" % (len(cands), out))

@@ -23,6 +23,7 @@ their ``z``, and a fold starts from their frequency derivative.
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
 """
 import optparse
 import os
@@ -34,12 +35,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
-                nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2):
+                nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2, maskfile=None,
+                rfifind=None):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
     pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
     acceleration search (pypulsar_amd.accel.AccelSearch, records of
-    ACCEL_CAND_DTYPE) on a z grid of ``dz``; ``harms`` then at most 16."""
+    ACCEL_CAND_DTYPE) on a z grid of ``dz``; ``harms`` then at most 16.
+    ``maskfile`` / ``rfifind``: the cells of that rfifind ``.mask``, or of the
+    one made here from the data with intervals of ``rfifind`` seconds (left as
+    <base>_rfifind.mask), are replaced by their channel's level first."""
     import torch
     from pypulsar_amd.formats import filterbank
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
@@ -53,6 +58,18 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     C, dt = fb.nchans, fb.tsamp * downsamp
     n = fb.number_of_samples // downsamp * downsamp
     raw = torch.from_numpy(fb.read_all_samples()[:n * C].reshape(n, C)).cuda()
+    if rfifind or maskfile:
+        from pypulsar_amd import rfi
+        if rfifind:
+            from pypulsar_amd.bin.rfifind import ptsperint_for
+            finder = rfi.RFIFind(ptsperint_for(rfifind, fb.tsamp))
+            mask = finder.mask_from_stats(*finder.stats(raw), **rfi.file_header(fb))
+            out = os.path.splitext(infile)[0] + "_rfifind.mask"
+            mask.write(out)
+            print("rfifind: %.2f%% masked -> %s" % (100.0 * mask.masked_fraction, out))
+        else:
+            mask = rfi.mask_from_file(maskfile, fb)
+        mask.apply(raw, 0)
     fb.close()
     # zero-DM + downsample + corner turn in one pass: [C, n / downsamp] float32
     img = torch.empty((C, n // downsamp), dtype=torch.float32, device=raw.device)
@@ -84,6 +101,12 @@ def main(argv=None):
                       help="Downsampling factor (divides 64). (Default: 1)")
     parser.add_option("--zero-dm", dest="zero_dm", action="store_true", default=False,
                       help="Apply the zero-DM filter first.")
+    parser.add_option("--mask", dest="maskfile", type="string", default=None,
+                      help="rfifind .mask file: its cells are replaced by the channel's "
+                           "level before anything else. (Default: no mask)")
+    parser.add_option("--rfifind", type="float", default=None, metavar="SECONDS",
+                      help="Make the mask from the data first, with intervals of SECONDS "
+                           "(written to <INFILE base>_rfifind.mask), then search with it.")
     parser.add_option("-s", "--sigma", type="float", default=6.0,
                       help="Single-trial candidate threshold in sigma. (Default: 6)")
     parser.add_option("--numharm", type="int", default=16,
@@ -123,7 +146,8 @@ def main(argv=None):
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
     res = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
                       options.flo, options.nfft, options.row_batch,
-                      return_plane=options.fold > 0, zmax=options.zmax, dz=options.dz)
+                      return_plane=options.fold > 0, zmax=options.zmax, dz=options.dz,
+                      maskfile=options.maskfile, rfifind=options.rfifind)
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]

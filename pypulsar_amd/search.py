@@ -131,9 +131,12 @@ class StreamingSearch(object):
     searched (they rotate by emitted block, so 2 suffice)."""
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm=True, dtype=None,
-                 threshold=6.0, widths=DEFAULT_WIDTHS, detrendlen=1024, max_cands=1 << 20):
+                 threshold=6.0, widths=DEFAULT_WIDTHS, detrendlen=1024, max_cands=1 << 20,
+                 rfimask=None):
         from .stream import StreamingSweep
         kw = {} if dtype is None else {"dtype": dtype}
+        if rfimask is not None:
+            kw["rfimask"] = rfimask
         self.sweep = StreamingSweep(dms, freqs, dt, block=block, downsamp=downsamp,
                                     zero_dm=zero_dm, **kw)
         self.search = SinglePulseSearch(threshold, widths, detrendlen, max_cands)

@@ -24,6 +24,7 @@ file order, 8/16-bit or float32):
     copy stream : pinned chunk i --H2D--> raw[i % 3][0:ov]      (head, event)
                   pinned chunk i --H2D--> raw[i % 3][ov:n]     (rest, event)
     compute     : raw[(i-1) % 3][block : block + ov] <- raw[i % 3][0 : ov]   (D2D)
+                  [rfimask.apply(raw[(i-1) % 3]): masked cells <- fill, in place]
                   prologue(raw[(i-1) % 3])  -> [C, (block + ov)/ds] u16 (or f32)
                   DMSweep (interleave + sweep, trim)   -> plane [D, block/ds]
 
@@ -72,8 +73,14 @@ class StreamingSweep(object):
     (downsampled time index)."""
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm="auto",
-                 dtype=torch.uint8, device="cuda"):
+                 dtype=torch.uint8, device="cuda", rfimask=None):
         _lib.require_gpu()
+        # rfimask: a pypulsar_amd.rfi.RFIMask applied in place to every raw
+        # block (at its absolute start sample) just before the prologue
+        self.rfimask = rfimask
+        if rfimask is not None:
+            assert rfimask.nchan == len(freqs), "the mask's channels are not the stream's"
+            assert dtype in (torch.uint8, torch.float32), "a mask needs 8-bit or float32 input"
         assert block % downsamp == 0 and 64 % downsamp == 0
         self.freqs = np.asarray(freqs, dtype=np.float64)
         self.C = len(self.freqs)
@@ -125,8 +132,11 @@ class StreamingSweep(object):
     def n_out_block(self):
         return self.block // self.ds
 
-    def _process(self, raw, n_valid, out=None):
-        """zero-DM + downsample + sweep of raw[:n_valid] -> plane (trim=True)."""
+    def _process(self, raw, n_valid, out=None, s0=0):
+        """zero-DM + downsample + sweep of raw[:n_valid] -> plane (trim=True);
+        s0: the block's first input sample (for the RFI mask)."""
+        if self.rfimask is not None:
+            self.rfimask.apply(raw[:n_valid], s0)
         nd = n_valid // self.ds
         n_out = max(0, nd - self.max_bin)
         if out is None:
@@ -152,6 +162,7 @@ class StreamingSweep(object):
         cur = torch.cuda.current_stream(self.device)
         prev = None  # (buffer index, n spectra)
         t0 = int(start_block) * self.n_out_block
+        s0 = int(start_block) * self.block  # first input sample of the block in `prev`
         i = -1
         emitted = 0
         for i, chunk in enumerate(chunks):
@@ -176,16 +187,17 @@ class StreamingSweep(object):
                     self.raw[pb][pn:pn + head].copy_(self.raw[b][:head])
                 out = None if planes is None else planes[emitted % len(planes)]
                 emitted += 1
-                plane = self._process(self.raw[pb], pn + head, out)
+                plane = self._process(self.raw[pb], pn + head, out, s0)
                 self.free[pb].record(cur)
                 yield t0, plane
                 t0 += plane.shape[1]
+                s0 += pn
             prev = (b, n)
         if prev is not None:
             pb, pn = prev
             cur.wait_event(self.h2d[pb])
             out = None if planes is None else planes[emitted % len(planes)]
-            plane = self._process(self.raw[pb], pn, out)
+            plane = self._process(self.raw[pb], pn, out, s0)
             self.free[pb].record(cur)
             yield t0, plane
 
