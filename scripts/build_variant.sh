@@ -3,11 +3,11 @@
 # (PDD_FX_GT, PDD_FX_PAIR_MAX, ...) into build/libpdd_<name>.so, loaded with
 # PDD_DEV_LIB=build/libpdd_<name>.so:  scripts/build_variant.sh <name> [-DFOO=1 ...]
 # (developer knobs -- stamps, timing-only decompositions: scripts/build_dev.sh)
+# Sources and flags: pypulsar_amd/_digest.py, the production build's own list.
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p build
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -fno-slp-vectorize \
-  -ffp-contract=off "$@" -o build/libpdd_$name.so \
-  pypulsar_amd/csrc/pdd_ops.hip pypulsar_amd/csrc/pdd_sweep.hip pypulsar_amd/csrc/pdd_search.hip \
-  pypulsar_amd/csrc/pdd_psrfits.hip pypulsar_amd/csrc/pdd_period.hip pypulsar_amd/csrc/pdd_fold.hip
+SRCS=$(python3 -c "from pypulsar_amd import _digest as d; print(' '.join('pypulsar_amd/csrc/' + s for s in d.SOURCES))")
+FLAGS=$(python3 -c "from pypulsar_amd import _digest as d; print(' '.join(d.FLAGS))")
+/opt/rocm/bin/hipcc $FLAGS "$@" -o build/libpdd_$name.so $SRCS

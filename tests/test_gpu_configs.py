@@ -371,7 +371,7 @@ def test_northstar_full_length(gpu, monkeypatch, D, factor, g_want):
     assert ds.pieces and ds.n_out == N - 14504 == 4179800
     gg, n_pat = ds.sw.factor_info(_lib.U8)
     assert gg == g_want and n_pat > 0, (gg, n_pat)
-    # delay-aligned tiles (pdd_sweep.hip fx_skew): trials skewed by up to
+    # delay-aligned tiles (pdd_sweep_plan.hip fx_skew): trials skewed by up to
     # their block's delay drift at the reference group
     assert ds.sw.skew_info(_lib.U8)[0] > 64
     ds.sw.set_timing(True)

@@ -232,7 +232,7 @@ def test_factor_f32_config1_geometry(gpu):
 @pytest.mark.parametrize("descending", [True, False])
 @pytest.mark.parametrize("mode", ["force4", "force2"])
 def test_factor_delay_aligned_tiles(gpu, pad, descending, mode):
-    """Delay-aligned factorised tiles (pdd_sweep.hip fx_skew): each trial's
+    """Delay-aligned factorised tiles (pdd_sweep_plan.hip fx_skew): each trial's
     time tile is skewed by its delay at a mid-band reference group, here by up
     to ~175 samples (two extra time tiles per segment), so tiles of one trial
     block store different column ranges and the first / last tiles store only

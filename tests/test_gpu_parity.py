@@ -391,10 +391,10 @@ def test_deepcopy_independent(S):
 
 
 # Every tiling the plan can choose, reached by a grid whose per-trial-block
-# shift span forces it (pdd_sweep.hip kF32Variants / kU8Variants, best first),
-# each checked against the oracle.  The dDM of each rung comes from the
-# plan-selection model tests/plan_model.py (asserted equal to the library's
-# choice): rung i selects candidate i.
+# shift span forces it (sweep_plan.h kF32Variants / kU8Variants, best first),
+# each checked against the oracle.  Rung i selects candidate i: asked of the
+# planner on the CPU (pdd_sweep_plan.hip through tests/native/plan_dump.cpp,
+# tests/test_sweep_plan.py) and asserted equal to the library's choice.
 LADDER = {"f32": [2.0, 8.0, 15.0, 40.0],
           "u8": [1.0, 3.0, 8.0, 15.0, 40.0]}
 
@@ -403,7 +403,7 @@ LADDER = {"f32": [2.0, 8.0, 15.0, 40.0],
 @pytest.mark.parametrize("dtype", ["f32", "u8"])
 def test_sweep_variant_ladder(gpu, dtype):
     import torch
-    import plan_model
+    from test_sweep_plan import run_plan
     from pypulsar_amd.sweep import DMSweep
     C, N, D = 32, 49152, 64
     freqs = band(C)
@@ -415,7 +415,7 @@ def test_sweep_variant_ladder(gpu, dtype):
     for want_v, ddm in enumerate(LADDER[dtype]):
         dms = np.arange(D) * ddm
         tab = orc.sweep_table(dms, freqs, DT)
-        assert plan_model.choose(tab, dtype) == want_v
+        assert run_plan(tab, code, 1)["variant"] == want_v
         sw = DMSweep(dms, freqs, DT, dtype=dtype)
         v = sw.info(code)["variant"]
         assert v == want_v, "dDM %g chose variant %d, expected %d" % (ddm, v, want_v)

@@ -164,29 +164,17 @@ def test_config2_two_stage_tables_match_reference(grids):
 
 def test_plan_model_ladder_covers_every_tiling():
     """The ladder grids of test_sweep_variant_ladder select every candidate
-    tiling (pdd_sweep.hip), in order, under the plan-selection model."""
-    import plan_model
+    tiling (sweep_plan.h kF32Variants / kU8Variants), in order: asked of the
+    planner itself (pdd_sweep_plan.hip through tests/native/plan_dump.cpp)."""
     from oracle import spectra_oracle as orc
     from test_gpu_parity import LADDER
+    from test_sweep_plan import run_plan
     freqs = band(32)
-    for dtype, cands in (("f32", plan_model.F32), ("u8", plan_model.U8)):
-        got = [plan_model.choose(orc.sweep_table(np.arange(64) * d, freqs, DT), dtype)
+    for dtype, code, n in (("f32", 0, 4), ("u8", 1, 5)):
+        got = [run_plan(orc.sweep_table(np.arange(64) * d, freqs, DT), code, 1)["variant"]
                for d in LADDER[dtype]]
-        assert got == list(range(len(cands))), (dtype, got)
-
-
-def test_plan_model_matches_kernel_tables():
-    """tests/plan_model.py restates the candidate tables of pdd_sweep.hip."""
-    import re
-    import plan_model
-    src = open(os.path.join(os.path.dirname(GOLDEN), "..", "pypulsar_amd", "csrc",
-                            "pdd_sweep.hip")).read()
-    for name, model in (("kF32Variants", plan_model.F32), ("kU8Variants", plan_model.U8)):
-        body = src[src.index("static const Variant %s[] = {" % name):]
-        body = body[:body.index("};")]
-        # rows under #ifdef PDD_SWEEP_DEV are developer-build tilings only
-        body = re.sub(r"#ifdef PDD_SWEEP_DEV.*?#endif", "", body, flags=re.S)
-        rows = [tuple(int(v) if v not in ("true", "false") else int(v == "true")
-                      for v in (x.strip() for x in m.split(",")))
-                for m in re.findall(r"\{([-\w, ]+)\}", body)]
-        assert rows == model, name
+        assert got == list(range(n)), (dtype, got)
+        # one rung per candidate: the last one is the last tiling of its list
+        # (a sparser grid still takes it: one trial per block, span 0)
+        sparser = run_plan(orc.sweep_table(np.arange(64) * 4000.0, freqs, DT), code, 1)
+        assert sparser["variant"] == n - 1
