@@ -476,6 +476,79 @@ int pdd_fold_search(const double* prof, const int32_t* cnt, const double* sumsq,
                     int npart, int nbins, int A, int B, double* chi2, int32_t* best,
                     double* best_chi2, double* best_prof, int32_t* best_cnt, void* stream);
 
+/* ---- fast-folding (FFA) search of a DM-time plane for long periods
+ * (pypulsar_amd/ffa.py; restated in tests/ffa_oracle.py).  A step of the plan
+ * searches base periods p0 = b_lo .. b_hi - 1 bins on the series downsampled
+ * by f.
+ *
+ * Prepare: y[i] = x[f i] + x[f i + 1] + .. + x[f i + f - 1], float32, ascending
+ * (a sum: integer rows stay integer), i < n_ds = n / f.  The series is cut
+ * into nchunk = max(1, n_ds / L) chunks of L samples, the last one running to
+ * the end; mean_c is the float64 mean of chunk c and ctr_c the mean index of
+ * its samples.  base(i) = mean_c + (mean_{c+1} - mean_c) (i - ctr_c) / (ctr_{c+1}
+ * - ctr_c) for ctr_c <= i < ctr_{c+1}, mean_0 before ctr_0 and mean_{nchunk-1}
+ * from ctr_{nchunk-1} on; y'[i] = float32(double(y[i]) - base(i)) and
+ * sigma^2 = sum(y'^2) / n_ds - (sum(y') / n_ds)^2 in float64 (sigma = 0 where
+ * that is not positive).  Sums of float64 run in a fixed order (deterministic).
+ *
+ * Transform of base period p0: M = n_ds / p0 rows y'[r p0 .. r p0 + p0) and
+ * zero rows up to Mp = 2^K = max(2, next power of two >= M).  The transform
+ * of one row is the row; two transformed half blocks head, tail of m / 2 rows
+ * merge into m rows
+ *   out[s][b] = head[s >> 1][b] + tail[s >> 1][(b + ((s + 1) >> 1)) mod p0],
+ * one float32 add per element and stage: bit-identical to the NumPy
+ * restatement for any input.  Trial s < Mp - 1 of the full transform is the
+ * fold at period (p0 + s / (Mp - 1)) bins.
+ *
+ * Score of a profile x of b = p0 bins: P[i] = x[0] + .. + x[i] and T = P[b - 1]
+ * in float32 (any association: exact for integer-valued profiles below 2^24),
+ * c(0) = 0, c(i) = P[i - 1].  For each width w of `widths` (ascending) with
+ * w <= max(1, floor(ducy_max b)) and w < b:
+ *   S_w = max over b0 < b of  c(b0 + w) - c(b0)                 (b0 + w <= b)
+ *                             (T - c(b0)) + c(b0 + w - b)        (otherwise),
+ *   snr_w = (S_w - w T / b) / (sigma sqrt(M w (1 - w / b)))       (float64; the
+ *           device multiplies by the reciprocals of b and of the denominator);
+ * the entry is float32 of the largest snr_w and the index of its width (the
+ * narrower on ties); 0 and index 0 where sigma == 0 or no width is admitted. */
+/* Host only (no GPU): info[4] = {M, K, kpass, npass} of base period p0 on a
+ * series of n_ds samples -- the K stages run as npass launches of
+ * pdd_ffa_pass, kpass stages each (the last one the rest), sized so that two
+ * buffers of 2^kpass rows of p0 floats fit the 160 KiB of LDS.  2 <= p0 <=
+ * 1024, 2 p0 <= n_ds < 2^31. */
+int pdd_ffa_plan_info(int64_t n_ds, int p0, int64_t* info);
+/* y[d][i] (i < n / f, contiguous rows) and mean[d][c] of the chunks of L
+ * downsampled samples, from rows x[d] of stride ld.  D < 65536. */
+int pdd_ffa_downsample(const float* x, int64_t D, int64_t n, int64_t ld, int64_t f, int64_t L,
+                       float* y, double* mean, void* stream);
+/* In place y -> y' with the means of pdd_ffa_downsample; part: [D][nchunk][2]
+ * float64 work area (the chunks' sums of y' and y'^2); sigma[d]. */
+int pdd_ffa_detrend(float* y, int64_t D, int64_t n_ds, int64_t L, const double* mean, double* part,
+                    double* sigma, void* stream);
+/* Pass `pass` (0 .. npass - 1) of the transforms of the D np problems (row d,
+ * base period p_lo + i), problem q = d np + i; base periods whose transform
+ * has fewer passes are skipped.  Pass 0 reads the rows of y ([D][n_ds], row stride ld); a
+ * later pass reads ws_in and a pass before the last writes ws_out, both
+ * [D np][slot] float32 with slot >= Mp p0 for every base period that uses
+ * them (two buffers alternate where npass > 2).  The last pass of a base
+ * period scores its profiles: snr / widx [D][ntrial] at trial toff[i] + s (toff:
+ * DEVICE int64 [np]; entries outside [0, ntrial) are not written); snr and
+ * widx null: no score.  prof (test hook, np == 1, may be null): the finished
+ * [D][Mp][p0] profiles.  widths: HOST int32 array, ascending, at most 16.
+ * D np < 65536. */
+int pdd_ffa_pass(const float* y, int64_t D, int64_t n_ds, int64_t ld, int p_lo, int np, int pass,
+                 const float* ws_in, float* ws_out, int64_t slot, const double* sigma,
+                 const int64_t* toff, const int32_t* widths, int n_widths, double ducy_max,
+                 float* snr, uint8_t* widx, int64_t ntrial, float* prof, void* stream);
+/* Trial k of snr [D][ntrial] (row stride ld) is a candidate when snr[k] >=
+ * threshold, snr[k] > snr[k-1] and snr[k] >= snr[k+1] (neighbours outside the
+ * row: -inf).  Records int32 {row, k, width index, float-bits snr} are
+ * appended through the device counter *count exactly as by pdd_ps_search
+ * (always incremented, stored while < max_cands: the caller checks for
+ * overflow). */
+int pdd_ffa_search(const float* snr, const uint8_t* widx, int64_t D, int64_t ntrial, int64_t ld,
+                   float threshold, int32_t* cands, int64_t max_cands, unsigned long long* count,
+                   void* stream);
+
 /* ---- RFI excision on the raw time-major block (pypulsar_amd/rfi.py; restated
  * in tests/rfi_oracle.py).  raw: [nint ptsperint][C] 8-bit or float32 (dtype
  * PDD_U8 / PDD_F32), row stride ld elements, cut into nint intervals of

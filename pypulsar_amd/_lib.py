@@ -53,7 +53,8 @@ EXPORTS = (
     "pdd_stream_destroy", "pdd_ps_prep", "pdd_ps_block_medians", "pdd_ps_normalise",
     "pdd_ps_harmsum", "pdd_ps_search", "pdd_fold_rows", "pdd_fold_search",
     "pdd_acc_correlate", "pdd_acc_search", "pdd_rfi_stats_prep", "pdd_rfi_stats_power",
-    "pdd_rfi_apply",
+    "pdd_rfi_apply", "pdd_ffa_plan_info", "pdd_ffa_downsample", "pdd_ffa_detrend", "pdd_ffa_pass",
+    "pdd_ffa_search",
 )
 
 
@@ -144,6 +145,12 @@ _SIGS = {
                            _int),
     "pdd_rfi_stats_power": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp], _int),
     "pdd_rfi_apply": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp], _int),
+    "pdd_ffa_plan_info": ([_i64, _int, _vp], _int),
+    "pdd_ffa_downsample": ([_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp], _int),
+    "pdd_ffa_detrend": ([_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp], _int),
+    "pdd_ffa_pass": ([_vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _vp, _int,
+                      ctypes.c_double, _vp, _vp, _i64, _vp, _vp], _int),
+    "pdd_ffa_search": ([_vp, _vp, _i64, _i64, _i64, ctypes.c_float, _vp, _i64, _vp, _vp], _int),
 }
 
 

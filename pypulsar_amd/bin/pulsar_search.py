@@ -17,13 +17,19 @@ neighbours, a search over period and period derivative) and written as
 ``<base>_cand<k>.bestprof`` and ``<base>_cand<k>.npz``.  With ``--zmax Z`` the
 rows are searched for signals that drift up to Z Fourier bins over the
 observation (pulsars in binaries; pypulsar_amd.accel): the candidates carry
-their ``z``, and a fold starts from their frequency derivative.
+their ``z``, and a fold starts from their frequency derivative.  With
+``--ffa`` the plane is also searched by fast folding (pypulsar_amd.ffa: slow,
+narrow pulses that the harmonic sums lose); its sifted candidates go to
+``<base>.ffacands`` in the same layout, and ``--fold K`` folds its K strongest
+as ``<base>_ffacand<k>``.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --ffa --ffa-pmin 0.5 --ffa-pmax 10 \\
+        --fold 3 obs.fil
 """
 import optparse
 import os
@@ -133,6 +139,25 @@ def main(argv=None):
                       help="Sub-integrations of a fold. (Default: 32)")
     parser.add_option("--fold-dm-halfwidth", dest="fold_dm_halfwidth", type="int", default=2,
                       help="DM trials folded on each side of a candidate's. (Default: 2)")
+    parser.add_option("--ffa", action="store_true", default=False,
+                      help="Also run the fast-folding search for slow pulsars on the plane; "
+                           "writes <base>.ffacands (and, with --fold K, "
+                           "<base>_ffacand<k>.bestprof and .npz).")
+    parser.add_option("--ffa-pmin", dest="ffa_pmin", type="float", default=0.5,
+                      help="Shortest fast-folded period in s. (Default: 0.5)")
+    parser.add_option("--ffa-pmax", dest="ffa_pmax", type="float", default=10.0,
+                      help="Longest fast-folded period in s. (Default: 10)")
+    parser.add_option("--ffa-bins-min", dest="ffa_bins_min", type="int", default=250,
+                      help="Fewest profile bins of a fast fold. (Default: 250)")
+    parser.add_option("--ffa-bins-max", dest="ffa_bins_max", type="int", default=500,
+                      help="Most profile bins of a fast fold. (Default: 500)")
+    parser.add_option("--ffa-snr", dest="ffa_snr", type="float", default=8.0,
+                      help="S/N threshold of a fast-folding candidate. (Default: 8)")
+    parser.add_option("--ffa-ducy", dest="ffa_ducy", type="float", default=0.2,
+                      help="Largest searched duty cycle. (Default: 0.2)")
+    parser.add_option("--ffa-detrend", dest="ffa_detrend", type="float", default=None,
+                      help="Length in s of the chunks whose means make the removed baseline. "
+                           "(Default: 4 x --ffa-pmax)")
     parser.add_option("-o", "--outname", default=None,
                       help="Output .accelcands file (default: INFILE with .accelcands).")
     options, args = parser.parse_args(argv)
@@ -146,7 +171,8 @@ def main(argv=None):
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
     res = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
                       options.flo, options.nfft, options.row_batch,
-                      return_plane=options.fold > 0, zmax=options.zmax, dz=options.dz,
+                      return_plane=options.fold > 0 or options.ffa, zmax=options.zmax,
+                      dz=options.dz,
                       maskfile=options.maskfile, rfifind=options.rfifind)
     cands = res[0]
     sifted = sift(cands)
@@ -158,24 +184,40 @@ def main(argv=None):
         fold_candidates(res[2], dms, res[1], sifted[:options.fold], os.path.splitext(out)[0],
                         args[0], options.fold_npart, options.fold_nbins,
                         options.fold_dm_halfwidth)
+    if options.ffa:
+        from pypulsar_amd.ffa import FFASearch
+        fs = FFASearch(options.ffa_pmin, options.ffa_pmax, options.ffa_bins_min,
+                       options.ffa_bins_max, options.ffa_snr, ducy_max=options.ffa_ducy,
+                       detrend=options.ffa_detrend)
+        fcands = fs(res[2], dms, res[1], row_batch=options.row_batch)
+        fsifted = sift(fcands)
+        fout = os.path.splitext(out)[0] + ".ffacands"
+        write_accelcands(fsifted, fout, basename=os.path.basename(base))
+        print("%d FFA candidates (%d sifted) -> %s" % (len(fcands), len(fsifted), fout))
+        if options.fold > 0:
+            fold_candidates(res[2], dms, res[1], fsifted[:options.fold], os.path.splitext(out)[0],
+                            args[0], options.fold_npart, options.fold_nbins,
+                            options.fold_dm_halfwidth, tag="ffacand")
     return 0
 
 
-def fold_candidates(plane, dms, dt, sifted, base, infile, npart=32, nbins=64, dm_halfwidth=2):
-    """Fold sifted candidates on the plane; writes ``<base>_cand<k>.bestprof``
-    and ``<base>_cand<k>.npz`` (k from 1, by descending sigma) and prints one
-    line per candidate.  Returns the FoldedCandidates."""
+def fold_candidates(plane, dms, dt, sifted, base, infile, npart=32, nbins=64, dm_halfwidth=2,
+                    tag="cand"):
+    """Fold sifted candidates on the plane; writes ``<base>_<tag><k>.bestprof``
+    and ``<base>_<tag><k>.npz`` (k from 1, by descending sigma; ``tag``:
+    ``cand``, or ``ffacand`` for those of the fast-folding search) and prints
+    one line per candidate.  Returns the FoldedCandidates."""
     from pypulsar_amd.fold import Folder, write_bestprof
     folded = Folder(npart, nbins)(plane, dms, dt, sifted, dm_halfwidth=dm_halfwidth)
     for k, fc in enumerate(folded, 1):
-        name = "%s_cand%d" % (base, k)
+        name = "%s_%s%d" % (base, tag, k)
         write_bestprof(fc, name + ".bestprof", infile=infile, candname=os.path.basename(name))
         np.savez(name + ".npz", subints=fc.subints, subint_counts=fc.subint_counts,
                  chi2_plane=fc.chi2_plane, chi2_vs_dm=fc.chi2_vs_dm, dms=fc.dms,
                  profile=fc.profile, counts=fc.counts, trial=np.asarray(fc.trial),
                  f=fc.f, fd=fc.fd, dm=fc.dm, chi2=fc.chi2, sigma=fc.sigma)
-        print("cand %d: DM %.2f  P %.9f ms  fd %.3g Hz/s  reduced chi2 %.2f  sigma %.1f -> %s" % (
-            k, fc.dm, 1000.0 * fc.period, fc.fd, fc.chi2, fc.sigma, name + ".bestprof"))
+        print("%s %d: DM %.2f  P %.9f ms  fd %.3g Hz/s  reduced chi2 %.2f  sigma %.1f -> %s" % (
+            tag, k, fc.dm, 1000.0 * fc.period, fc.fd, fc.chi2, fc.sigma, name + ".bestprof"))
     return folded
 
 
