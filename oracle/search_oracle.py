@@ -45,12 +45,16 @@ def boxcar_snr(z, w):
     return (c[:, w:] - c[:, :-w]) / np.sqrt(w)
 
 
-def search(x, widths, threshold, L, window=WINDOW):
+def search(x, widths, threshold, L, window=WINDOW, n_starts=None):
     """Candidates [(row, start, width, snr)] sorted by (row, start), plus the
     per-window margin between the best and the runner-up (width, start) --
-    tests skip exact (start, width) comparison for near-ties."""
+    tests skip exact (start, width) comparison for near-ties.  With n_starts
+    only the starts t < n_starts compete (the window holding n_starts takes
+    its maximum over the starts below it); their boxcars still extend up to
+    the row's end n."""
     z = normalise(x, L)
     D, n = z.shape
+    ns = n if n_starts is None else min(int(n_starts), n)
     nwin = -(-n // window)
     best = np.full((D, nwin), -np.inf)
     second = np.full((D, nwin), -np.inf)
@@ -59,7 +63,7 @@ def search(x, widths, threshold, L, window=WINDOW):
     for w in widths:
         if w > n:
             break
-        s = boxcar_snr(z, w)  # [D, n-w+1]
+        s = boxcar_snr(z, w)[:, :ns]  # [D, min(n-w+1, ns)]
         m = s.shape[1]
         pad = nwin * window - m
         sp = np.concatenate([s, np.full((D, pad), -np.inf)], axis=1).reshape(D, nwin, window)

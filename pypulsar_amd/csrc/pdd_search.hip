@@ -19,13 +19,28 @@
 //
 // Kernels (each reads the plane once; k_sp_search is VALU-bound, DESIGN.md
 // §6b):
-//   k_sp_stats   one wave per chunk: single-pass shifted sums, one butterfly
+//   k_sp_stats   one wave per chunk: single-pass sums shifted by a pilot mean,
+//                one butterfly
 //   k_sp_search  one 256-thread block per (row, 4 windows of 1024 starts): z
 //                of the starts + halo (max width - 1) into LDS, block prefix
 //                sum (exclusive, relative to the block start), then every
 //                (start, width) is one LDS difference; per-window max, then
 //                an exact arg-max pass only for windows over the threshold;
 //                compact candidate list through one atomic counter.
+//
+// Accuracy against the float64 definition, as tests/test_gpu_search_paths.py
+// pins it (bars; worst measured on the MI355X in DESIGN.md §6b):
+//   1/std        <= 1e-4 relative, also with a 100-300 sigma outlier at the
+//                chunk's first sample and at L up to 5000 (measured < 5e-7);
+//   mean         |d mean| / std * sqrt(150) <= 1e-4 * threshold beyond its f32
+//                representation (measured: inside the representation);
+//   S/N          <= 1e-4 * max(1, |s|) + sqrt(w) * ulp(mean)/2 / std.
+// The last term is a limit of the f32 mean, not of the sums: x - mean is
+// exact for an integer plane, but the stored mean is rounded to ulp/2, and a
+// boxcar adds that offset w times.  At a mean of 2^19 (4096 channels x 128)
+// ulp/2 = 1/32: sqrt(w) / (32 std), i.e. 6e-3 at std 64 and w = 150, 4e-4 at
+// std 1024.  Planes with std below ~100 at that mean miss the plain 1e-4 bar
+// on wide boxcars of moderate S/N.
 #include <algorithm>
 #include <cmath>
 
@@ -76,10 +91,16 @@ __device__ __forceinline__ float wave_reduce0(float v, Op op) {
 }
 
 // one wave per (row, chunk), 4 per block: the chunk is read once, coalesced,
-// as shifted sums S1 = sum(x - K), S2 = sum((x - K)^2) with K the chunk's
-// first sample, so var = S2/len - (S1/len)^2 does not cancel against a large
-// mean (plane rows sit at ~C x 128 for 8-bit input) and f32 is enough; both
-// sums go through one butterfly reduction (wave_reduce0).
+// as shifted sums S1 = sum(x - K), S2 = sum((x - K)^2), so var = S2/len -
+// (S1/len)^2 does not cancel against a large mean (plane rows sit at ~C x 128
+// for 8-bit input) and f32 is enough; the sums go through one butterfly
+// reduction (wave_reduce0).  The shift K is a pilot mean: of samples 0, 4,
+// 8, ... of the chunk's first 256, taken from the first pass's registers (no
+// further load) through the same butterfly.  A single sample moves it by
+// 1/64 of its height, where K = row[0] took an outlier there whole (a 300
+// sigma spike at a chunk start put m1^2 = 9e4 var into the subtraction:
+// 1/std off by 6e-4 at L = 4096).  With j of the pilot samples contaminated
+// the cancellation S2/len : var stays below 1 + j L / 4096.
 __global__ __launch_bounds__(256) void k_sp_stats(const float* __restrict__ x, int64_t D, int64_t n,
                                                   int64_t ld, int64_t L, int64_t nchunk,
                                                   float* __restrict__ mean_out,
@@ -91,14 +112,19 @@ __global__ __launch_bounds__(256) void k_sp_stats(const float* __restrict__ x, i
   const int64_t t0 = k * L;
   const int len = (int)((t0 + L <= n) ? L : n - t0);
   const float* row = x + d * ld + t0;
-  const float K = row[0];
   // lane l sums samples 4 (l + 64 i) + e in (i, e) order, by 16-byte loads
   // where the chunk start is 16-byte aligned and its length a multiple of 4,
   // by single loads otherwise: the same float sums either way (a streamed
   // plane's chunks land at other alignments than the one-shot plane's).
   // Loads past the chunk re-read its last group / sample (in bounds) and add
   // K (i.e. 0), so each pass issues its loads before any use.
-  float s1 = 0.f, s2 = 0.f;
+  const auto plus = [](float a, float b) { return a + b; };
+  float s1 = 0.f, s2 = 0.f, K = 0.f;
+  // (lane l < np holds sample 4 l in a[0][0] on both load paths)
+  auto pilot = [&](const float (&a)[4][4]) {
+    const int np = min(64, (len + 3) >> 2);
+    K = wave_reduce0(lane < np ? a[0][0] : 0.f, plus) / (float)np;
+  };
   auto add = [&](const float (&a)[4][4], int i0) {
 #pragma unroll
     for (int u = 0; u < 4; ++u)
@@ -120,6 +146,7 @@ __global__ __launch_bounds__(256) void k_sp_stats(const float* __restrict__ x, i
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[u][e] = q[e];
       }
+      if (i0 == 0) pilot(a);
       add(a, i0);
     }
   } else {
@@ -129,10 +156,10 @@ __global__ __launch_bounds__(256) void k_sp_stats(const float* __restrict__ x, i
       for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[u][e] = row[min(4 * (lane + 64 * (i0 + u)) + e, len - 1)];
+      if (i0 == 0) pilot(a);
       add(a, i0);
     }
   }
-  const auto plus = [](float a, float b) { return a + b; };
   s1 = wave_reduce0(s1, plus);
   s2 = wave_reduce0(s2, plus);
   if (lane == 0) {

@@ -8,25 +8,11 @@ import pytest
 
 from conftest import band, u8_data
 from oracle import search_oracle as so
+from search_check import check as _check
 
 pytestmark = pytest.mark.gpu
 WIDTHS = (1, 2, 3, 4, 6, 9, 14, 20, 30, 45, 70, 100, 150)
 DT = 64e-6
-
-
-def _check(gpu_c, ora, margins, thr):
-    og = {(d, t // 1024): (t, w, s, m) for (d, t, w, s), m in zip(ora, margins)}
-    gg = {(int(r), int(t) // 1024): (int(t), int(w), float(s))
-          for r, t, w, s in zip(gpu_c["row"], gpu_c["Sample"], gpu_c["Downfact"], gpu_c["Sigma"])}
-    for k in set(og) | set(gg):
-        if k in og and k in gg:
-            t, w, s, m = og[k]
-            assert abs(gg[k][2] - s) <= 1e-4 * max(1.0, abs(s)), (k, gg[k], og[k])
-            if m > 1e-4 * abs(s):
-                assert gg[k][:2] == (t, w), (k, gg[k], og[k])
-        else:  # only allowed at the threshold
-            s = og[k][2] if k in og else gg[k][2]
-            assert abs(s - thr) <= 1e-4 * abs(thr), (k, s)
 
 
 @pytest.mark.parametrize("D,n,L", [(7, 5000, 1000), (3, 1024, 256), (2, 777, 1000),

@@ -57,6 +57,50 @@ def test_tie_breaks_smallest_width_then_start():
     assert cands[0][1] == 100 and cands[0][2] == 1
 
 
+def test_start_limit_multiple_of_window_filters_full_search():
+    """n_starts a multiple of 1024: whole windows drop out, the others keep
+    their candidates and margins (boxcars reaching past the limit included)."""
+    D, n, L = 5, 5000, 1000
+    x = noise(D, n, 7)
+    for d, t, w, a in [(0, 1000, 30, 2.0), (1, 2040, 20, 3.0), (2, 3060, 9, 4.0),
+                       (3, 4090, 4, 6.0), (4, 10, 1, 9.0), (4, 4999, 1, 9.0)]:
+        x[d, t:t + w] += a
+    full, fm = so.search(x, WIDTHS, 4.0, L)
+    assert len(full) >= 6
+    for ns in (1024, 2048, 4096):
+        lim, lm = so.search(x, WIDTHS, 4.0, L, n_starts=ns)
+        keep = [i for i, c in enumerate(full) if c[1] < ns]
+        assert 0 < len(keep) < len(full)
+        assert lim == [full[i] for i in keep] and lm == [fm[i] for i in keep]
+    for ns in (None, n, n + 100):
+        assert so.search(x, WIDTHS, 4.0, L, n_starts=ns) == (full, fm)
+    assert so.search(x, WIDTHS, 4.0, L, n_starts=0) == ([], [])
+
+
+def test_start_limit_hand_checked():
+    """n_starts inside window 1: a spike A = 50 at 1500, a spike B = 20 at
+    1400 on +1, -1 alternation, widths (1, 2), one chunk.  Only starts below
+    the limit compete, but their boxcars may reach past it: with the limit at
+    1500 the winner is the w = 2 boxcar from 1499 that takes A in."""
+    n = 2048
+    x = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)[None, :].copy()
+    x[0, 1500], x[0, 1400] = 50.0, 20.0
+    z = (x[0] - x[0].mean()) / x[0].std()
+    for ns, want in [(1501, (0, 1500, 1, z[1500])),
+                     (1500, (0, 1499, 2, (z[1499] + z[1500]) / np.sqrt(2.0))),
+                     (1499, (0, 1400, 1, z[1400])),
+                     (1401, (0, 1400, 1, z[1400])),
+                     (1400, (0, 1399, 2, (z[1399] + z[1400]) / np.sqrt(2.0))),
+                     (1399, None), (1025, None)]:
+        cands, _ = so.search(x, (1, 2), 3.0, n, n_starts=ns)
+        assert len(cands) == (0 if want is None else 1), (ns, cands)
+        if want is not None:
+            assert cands[0][:3] == want[:3], (ns, cands)
+            assert abs(cands[0][3] - want[3]) < 1e-12
+    # window 0 holds nothing over the threshold whatever the limit
+    assert so.search(x, (1, 2), 3.0, n, n_starts=1)[0] == []
+
+
 def test_records_roundtrip(tmp_path):
     from pypulsar_amd import search
     raw = np.array([[2, 30, 4, 0], [0, 10, 1, 0]], dtype=np.int32)
