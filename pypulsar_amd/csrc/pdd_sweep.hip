@@ -485,82 +485,30 @@ struct InLayout {
   }
 };
 
+// Sample sources of the pre-pass and of stage 1: at(c, s) = sample s of
+// channel c.  Rows of uint8_t / uint16_t / float in an InLayout ...
 template <typename InT>
-__global__ __launch_bounds__(256) void k_interleave(const InT* __restrict__ x, InLayout lay, int64_t N,
-                                                    int64_t base, int64_t Qs, int64_t nR,
-                                                    int pad_mode, const float* __restrict__ padvals,
-                                                    float4* __restrict__ R) {
-  const int c = blockIdx.y;
-  const int64_t j0 = (int64_t)blockIdx.x * (256 * kIlPer) + threadIdx.x;
-  const float pv = (pad_mode == PDD_PAD_VALUE) ? padvals[c] : 0.f;
-  float v[kIlPer][4];
-#pragma unroll
-  for (int i = 0; i < kIlPer; ++i)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t s = base + j0 + i * 256 + k * Qs;
-      if (s >= 0 && s < N) v[i][k] = (float)x[lay.at(c, s)];
-      else if (pad_mode == PDD_PAD_ROTATE) v[i][k] = (float)x[lay.at(c, wrap_mod(s, N))];
-      else v[i][k] = pv;
-    }
-#pragma unroll
-  for (int i = 0; i < kIlPer; ++i) {
-    const int64_t j = j0 + i * 256;
-    if (j < nR) R[(int64_t)c * nR + j] = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
-  }
-}
-
-// u16 eighths for 8-bit data (and for 16-bit data <= 1023): R[c][j] = 8
-// samples X(c, b + j + k*Qs), k < 8, as packed u16 pairs (word h = sample 2h |
-// sample 2h+1 << 16); pads (integer values, checked by the caller) and
-// rotation baked in as for float32.
-template <typename InT>
-__global__ __launch_bounds__(256) void k_interleave_u16(const InT* __restrict__ x, InLayout lay,
-                                                        int64_t N, int64_t base, int64_t Qs,
-                                                        int64_t nR, int pad_mode,
-                                                        const float* __restrict__ padvals,
-                                                        uint4* __restrict__ R) {
-  const int c = blockIdx.y;
-  const int64_t j0 = (int64_t)blockIdx.x * (256 * kIlPer) + threadIdx.x;
-  const uint32_t pv = (pad_mode == PDD_PAD_VALUE) ? (uint32_t)padvals[c] : 0u;
-  uint32_t v[kIlPer][8];
-#pragma unroll
-  for (int i = 0; i < kIlPer; ++i)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t s = base + j0 + i * 256 + k * Qs;
-      if (s >= 0 && s < N) v[i][k] = x[lay.at(c, s)];
-      else if (pad_mode == PDD_PAD_ROTATE) v[i][k] = x[lay.at(c, wrap_mod(s, N))];
-      else v[i][k] = pv;
-    }
-#pragma unroll
-  for (int i = 0; i < kIlPer; ++i) {
-    const int64_t j = j0 + i * 256;
-    if (j < nR)
-      R[(int64_t)c * nR + j] = make_uint4(v[i][0] | (v[i][1] << 16), v[i][2] | (v[i][3] << 16),
-                                          v[i][4] | (v[i][5] << 16), v[i][6] | (v[i][7] << 16));
-  }
-}
-
-// The same u16 eighths of an 8-bit block DOWNSAMPLED by F <= 4 on the fly
+struct SrcRows {
+  const InT* x;
+  InLayout lay;
+  __device__ __forceinline__ SrcRows(const void* xv, const InLayout& l)
+      : x(static_cast<const InT*>(xv)), lay(l) {}
+  __device__ __forceinline__ InT at(int c, int64_t s) const { return x[lay.at(c, s)]; }
+};
+// ... or an 8-bit block DOWNSAMPLED by F <= 4 on the fly
 // (formats/spectra.py:329-351: sample s = the co-add of raw samples
 // s*F .. s*F + F - 1, <= 1020, exact), so a downsampled DDplan step never
 // writes and re-reads its downsampled copy; pads and rotation act on the
-// downsampled series (N = raw length / F) as for k_interleave_u16.  VEC: the
-// F raw bytes of a sample are one aligned 2- or 4-byte load (summed by
-// v_sad_u8 against zero).
+// downsampled series (N = raw length / F).  VEC: the F raw bytes of a sample
+// are one aligned 2- or 4-byte load (summed by v_sad_u8 against zero).
 template <int F, bool VEC>
-__global__ __launch_bounds__(256) void k_interleave_u16_ds(const uint8_t* __restrict__ x, int64_t ld,
-                                                           int64_t N, int64_t base, int64_t Qs,
-                                                           int64_t nR, int pad_mode,
-                                                           const float* __restrict__ padvals,
-                                                           uint4* __restrict__ R) {
-  const int c = blockIdx.y;
-  const int64_t j0 = (int64_t)blockIdx.x * (256 * kIlPer) + threadIdx.x;
-  const uint32_t pv = (pad_mode == PDD_PAD_VALUE) ? (uint32_t)padvals[c] : 0u;
-  const uint8_t* row = x + (int64_t)c * ld;
-  auto coadd = [&](int64_t s) -> uint32_t {
-    const uint8_t* q = row + s * F;
+struct SrcCoadd {
+  const uint8_t* x;
+  int64_t ld;
+  __device__ __forceinline__ SrcCoadd(const void* xv, const InLayout& l)
+      : x(static_cast<const uint8_t*>(xv)), ld(l.ld) {}
+  __device__ __forceinline__ uint32_t at(int c, int64_t s) const {
+    const uint8_t* q = x + (int64_t)c * ld + s * F;
     if constexpr (VEC && F == 4) {
       return __builtin_amdgcn_sad_u8(*reinterpret_cast<const uint32_t*>(q), 0u, 0u);
     } else if constexpr (VEC && F == 2) {
@@ -571,23 +519,82 @@ __global__ __launch_bounds__(256) void k_interleave_u16_ds(const uint8_t* __rest
       for (int k = 0; k < F; ++k) a += q[k];
       return a;
     }
-  };
-  uint32_t v[kIlPer][8];
+  }
+};
+
+// The two element kinds: float32 QUARTERS (4 samples Qs apart) and, for 8-bit
+// data (and 16-bit data <= 1023), u16 EIGHTHS: 8 samples as packed u16 pairs
+// (word h = sample 2h | sample 2h+1 << 16; pads are integers, checked by the
+// caller).  add: one pattern term of stage 1, component by component.
+struct ElemF32 {
+  using value_t = float;
+  using elem_t = float4;
+  static constexpr int S = 4;
+  static __device__ __forceinline__ float4 pack(const float (&v)[4]) {
+    return make_float4(v[0], v[1], v[2], v[3]);
+  }
+  static __device__ __forceinline__ float4 add(float4 a, const float4& b) {
+    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    return a;
+  }
+};
+struct ElemU16 {
+  using value_t = uint32_t;
+  using elem_t = uint4;
+  static constexpr int S = 8;
+  static __device__ __forceinline__ uint4 pack(const uint32_t (&v)[8]) {
+    return make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16),
+                      v[6] | (v[7] << 16));
+  }
+  static __device__ __forceinline__ uint4 add(const uint4& a, const uint4& b) {
+    return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+  }
+};
+
+// The reference pad semantics, once: inside [0, N) the data, else the
+// rotated sample or the channel's pad value.
+template <typename V>
+__device__ __forceinline__ V pad_value(int pad_mode, const float* __restrict__ padvals, int c) {
+  return (pad_mode == PDD_PAD_VALUE) ? (V)padvals[c] : (V)0;
+}
+template <typename V, typename Src>
+__device__ __forceinline__ V padded_sample(const Src& src, int c, int64_t s, int64_t N,
+                                           int pad_mode, V pv) {
+  if (s >= 0 && s < N) return (V)src.at(c, s);
+  if (pad_mode == PDD_PAD_ROTATE) return (V)src.at(c, wrap_mod(s, N));
+  return pv;
+}
+
+// Arguments of every pre-pass instance (x: the input of the instance's
+// source; R: float4 or uint4 elements, the same 16 bytes), so one table
+// (kIlInstances) selects and launches them.
+struct IlArgs {
+  const void* x;
+  InLayout lay;
+  int64_t N, base, Qs, nR;
+  int pad_mode;
+  const float* padvals;
+  void* R;
+};
+
+template <typename Src, typename El>
+__global__ __launch_bounds__(256) void k_interleave(const IlArgs a) {
+  using V = typename El::value_t;
+  const Src src(a.x, a.lay);
+  const int c = blockIdx.y;
+  const int64_t j0 = (int64_t)blockIdx.x * (256 * kIlPer) + threadIdx.x;
+  const V pv = pad_value<V>(a.pad_mode, a.padvals, c);
+  V v[kIlPer][El::S];
 #pragma unroll
   for (int i = 0; i < kIlPer; ++i)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int64_t s = base + j0 + i * 256 + k * Qs;
-      if (s >= 0 && s < N) v[i][k] = coadd(s);
-      else if (pad_mode == PDD_PAD_ROTATE) v[i][k] = coadd(wrap_mod(s, N));
-      else v[i][k] = pv;
-    }
+    for (int k = 0; k < El::S; ++k)
+      v[i][k] = padded_sample<V>(src, c, a.base + j0 + i * 256 + k * a.Qs, a.N, a.pad_mode, pv);
+  typename El::elem_t* R = static_cast<typename El::elem_t*>(a.R);
 #pragma unroll
   for (int i = 0; i < kIlPer; ++i) {
     const int64_t j = j0 + i * 256;
-    if (j < nR)
-      R[(int64_t)c * nR + j] = make_uint4(v[i][0] | (v[i][1] << 16), v[i][2] | (v[i][3] << 16),
-                                          v[i][4] | (v[i][5] << 16), v[i][6] | (v[i][7] << 16));
+    if (j < a.nR) R[(int64_t)c * a.nR + j] = El::pack(v[i]);
   }
 }
 
@@ -597,56 +604,66 @@ __global__ __launch_bounds__(256) void k_interleave_u16_ds(const uint8_t* __rest
 // piece); the element run's base must be a multiple of J (base % J == 0,
 // Qs % J == 0).  Runs that touch a pad or the wrap take the per-sample path.
 template <int F>
-__global__ __launch_bounds__(256) void k_interleave_u16_ds_v(const uint8_t* __restrict__ x,
-                                                             int64_t ld, int64_t N, int64_t base,
-                                                             int64_t Qs, int64_t nR, int pad_mode,
-                                                             const float* __restrict__ padvals,
-                                                             uint4* __restrict__ R) {
+__global__ __launch_bounds__(256) void k_interleave_u16_ds_v(const IlArgs a) {
   static_assert(F == 2 || F == 4, "16-byte loads of 4 or 8 co-adds");
   constexpr int J = 16 / F;
+  const SrcCoadd<F, false> src(a.x, a.lay);
   const int c = blockIdx.y;
   const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * J;
-  if (j0 >= nR) return;
-  const uint32_t pv = (pad_mode == PDD_PAD_VALUE) ? (uint32_t)padvals[c] : 0u;
-  const uint8_t* row = x + (int64_t)c * ld;
-  uint32_t v[8][J];
+  if (j0 >= a.nR) return;
+  const uint32_t pv = pad_value<uint32_t>(a.pad_mode, a.padvals, c);
+  const uint8_t* row = src.x + (int64_t)c * src.ld;
+  uint32_t v[J][8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const int64_t s0 = base + j0 + k * Qs;
-    if (s0 >= 0 && s0 + J <= N) {
+    const int64_t s0 = a.base + j0 + k * a.Qs;
+    if (s0 >= 0 && s0 + J <= a.N) {
       const uint4 q = *reinterpret_cast<const uint4*>(row + s0 * F);
       const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
         if constexpr (F == 4) {
-          v[k][h] = __builtin_amdgcn_sad_u8(w[h], 0u, 0u);
+          v[h][k] = __builtin_amdgcn_sad_u8(w[h], 0u, 0u);
         } else {
-          v[k][2 * h] = __builtin_amdgcn_sad_u8(w[h] & 0xffffu, 0u, 0u);
-          v[k][2 * h + 1] = __builtin_amdgcn_sad_u8(w[h] >> 16, 0u, 0u);
+          v[2 * h][k] = __builtin_amdgcn_sad_u8(w[h] & 0xffffu, 0u, 0u);
+          v[2 * h + 1][k] = __builtin_amdgcn_sad_u8(w[h] >> 16, 0u, 0u);
         }
       }
     } else {
 #pragma unroll
-      for (int e = 0; e < J; ++e) {
-        const int64_t s = s0 + e;
-        const int64_t sw = (s >= 0 && s < N) ? s : (pad_mode == PDD_PAD_ROTATE ? wrap_mod(s, N) : -1);
-        uint32_t a = pv;
-        if (sw >= 0) {
-          a = 0;
-#pragma unroll
-          for (int f = 0; f < F; ++f) a += row[sw * F + f];
-        }
-        v[k][e] = a;
-      }
+      for (int e = 0; e < J; ++e) v[e][k] = padded_sample<uint32_t>(src, c, s0 + e, a.N, a.pad_mode, pv);
     }
   }
-  uint4* dst = R + (int64_t)c * nR + j0;
+  uint4* dst = static_cast<uint4*>(a.R) + (int64_t)c * a.nR + j0;
 #pragma unroll
   for (int e = 0; e < J; ++e)
-    if (j0 + e < nR)
-      dst[e] = make_uint4(v[0][e] | (v[1][e] << 16), v[2][e] | (v[3][e] << 16),
-                          v[4][e] | (v[5][e] << 16), v[6][e] | (v[7][e] << 16));
+    if (j0 + e < a.nR) dst[e] = ElemU16::pack(v[e]);
 }
+
+// Every pre-pass instance: (downsampling factor, vector form, plan dtype,
+// element kind) -> kernel and the elements one of its blocks builds.  vec:
+// 16 = the J-consecutive form, 1 = aligned F-byte co-add loads, 0 = bytes.
+typedef void (*il_fn)(IlArgs);
+struct IlInstance {
+  int ds, vec, dtype;
+  bool u16;
+  il_fn fn;
+  int per_block;
+};
+static const IlInstance kIlInstances[] = {
+    {1, 0, PDD_U8, true, k_interleave<SrcRows<uint8_t>, ElemU16>, 256 * kIlPer},
+    {1, 0, PDD_U16, true, k_interleave<SrcRows<uint16_t>, ElemU16>, 256 * kIlPer},
+    {1, 0, PDD_U8, false, k_interleave<SrcRows<uint8_t>, ElemF32>, 256 * kIlPer},
+    {1, 0, PDD_U16, false, k_interleave<SrcRows<uint16_t>, ElemF32>, 256 * kIlPer},
+    {1, 0, PDD_F32, false, k_interleave<SrcRows<float>, ElemF32>, 256 * kIlPer},
+    {2, 16, PDD_U16, true, k_interleave_u16_ds_v<2>, 256 * 8},
+    {4, 16, PDD_U16, true, k_interleave_u16_ds_v<4>, 256 * 4},
+    {2, 1, PDD_U16, true, k_interleave<SrcCoadd<2, true>, ElemU16>, 256 * kIlPer},
+    {2, 0, PDD_U16, true, k_interleave<SrcCoadd<2, false>, ElemU16>, 256 * kIlPer},
+    {3, 0, PDD_U16, true, k_interleave<SrcCoadd<3, false>, ElemU16>, 256 * kIlPer},
+    {4, 1, PDD_U16, true, k_interleave<SrcCoadd<4, true>, ElemU16>, 256 * kIlPer},
+    {4, 0, PDD_U16, true, k_interleave<SrcCoadd<4, false>, ElemU16>, 256 * kIlPer},
+};
 
 // ------------------------------------------------------------------ factorised sweep
 // Exact factorisation of the 8-bit sweep over groups of fx = 4 (or 2)
@@ -714,179 +731,109 @@ __device__ __forceinline__ FxBatch fx_batch(const int4* __restrict__ pat, const 
   const int4 q = pat[pl];
   return {q.y, q.z, q.w, rng[2 * pl], rng[2 * pl + 1]};
 }
-__global__ __launch_bounds__(256) void k_fx_patterns_lds(const uint4* __restrict__ R, int64_t nR,
-                                                         const int4* __restrict__ pat,
-                                                         const int* __restrict__ gtab, int NG,
-                                                         int fx, uint4* __restrict__ P) {
-  extern __shared__ __attribute__((aligned(16))) uint4 L[];
-  const int g = blockIdx.x;
-  const int64_t j0 = (int64_t)blockIdx.y * kFxE;
-  const int p0 = gtab[g], p1 = gtab[g + 1];
-  const int lo = gtab[NG + 1 + 2 * g], hi = gtab[NG + 2 + 2 * g];
-  const int W = kFxE + hi - lo;
-  const uint4* r0 = R + (int64_t)(g * fx) * nR;
-  for (int k = 0; k < fx; ++k)
+
+// Arguments of every LDS stage-1 instance: the pre-pass's (x: the
+// u16-eighths image or the sweep's input; lay .. padvals only for the input
+// sources; R: the pattern image, uint4 or float4 elements) and the plan's
+// tables, so one table (kFxS1Instances) sets their LDS limits and launches them.
+struct FxS1Args : IlArgs {
+  const int4* pat;
+  const int* gtab;
+  int NG;
+};
+
+// Stage-1 sources.  load_row fills one LDS row with the elements [i0, i0 + W)
+// of channel c's image row (zeros outside [0, nR): elements no trial reads).
+// The image rows a pre-pass wrote (R in HBM: downsampled input) ...
+struct FxFromImage {
+  using El = ElemU16;
+  static constexpr int kBlock = kFxE;
+  static constexpr bool kNontemporal = false;
+  const uint4* R;
+  int64_t nR;
+  __device__ __forceinline__ explicit FxFromImage(const FxS1Args& a)
+      : R(static_cast<const uint4*>(a.x)), nR(a.nR) {}
+  __device__ __forceinline__ void load_row(uint4* L, int c, int64_t i0, int W) const {
     for (int e = threadIdx.x; e < W; e += 256) {
-      const int64_t i = j0 + lo + e;
-      L[k * W + e] = (i >= 0 && i < nR) ? r0[(int64_t)k * nR + i] : make_uint4(0u, 0u, 0u, 0u);
-    }
-  __syncthreads();
-  const int* rng = gtab + 3 * NG + 1;
-  for (int pb = p0; pb < p1; pb += 64) {
-    const FxBatch B = fx_batch(pat, rng, pb, p1);
-    for (int i = 0; i < min(64, p1 - pb); ++i) {
-      const int p = pb + i;
-      const int4 q = make_int4(0, __builtin_amdgcn_readlane(B.y, i), __builtin_amdgcn_readlane(B.z, i),
-                               __builtin_amdgcn_readlane(B.w, i));
-      const int64_t jlo = __builtin_amdgcn_readlane(B.lo, i), jhi = nR + __builtin_amdgcn_readlane(B.hi, i);
-      if (j0 >= jhi || j0 + kFxE <= jlo) continue;  // no trial of p reads this block
-#pragma unroll
-      for (int e = threadIdx.x; e < kFxE; e += 256) {
-        const int64_t j = j0 + e;
-        if (j >= nR) break;  // (a block's elements outside [jlo, jhi): written, unread)
-        const uint4 a = L[e - lo], b = L[W + e - lo + q.y];
-        const uint4 c = fx > 2 ? L[2 * W + e - lo + q.z] : make_uint4(0u, 0u, 0u, 0u);
-        const uint4 d = fx > 3 ? L[3 * W + e - lo + q.w] : make_uint4(0u, 0u, 0u, 0u);
-        P[(int64_t)p * nR + j] = make_uint4(a.x + b.x + c.x + d.x, a.y + b.y + c.y + d.y,
-                                            a.z + b.z + c.z + d.z, a.w + b.w + c.w + d.w);
-      }
+      const int64_t i = i0 + e;
+      L[e] = (i >= 0 && i < nR) ? R[(int64_t)c * nR + i] : make_uint4(0u, 0u, 0u, 0u);
     }
   }
-}
-
-// Stage 1 straight from the input (no u16-eighths image R in HBM): the
-// load phase builds each of the group's row elements the way
-// k_interleave_u16 would -- 8 samples X(c, base + i + m*Qs), m < 8, as packed
-// u16 pairs, with the reference pads (value / rotate) -- then writes every
-// pattern of the group as k_fx_patterns_lds does.  Saves the image's write
-// and read, and the interleave launch, per segment (the per-rank work of a
-// DM-sharded step that does not shrink with the world size).
-template <typename InT, int FXG>
-__global__ __launch_bounds__(256) void k_fx_patterns_x(const InT* __restrict__ x, InLayout lay,
-                                                       int64_t N, int64_t base, int64_t Qs,
-                                                       int64_t nR, int pad_mode,
-                                                       const float* __restrict__ padvals,
-                                                       const int4* __restrict__ pat,
-                                                       const int* __restrict__ gtab, int NG, int fx,
-                                                       uint4* __restrict__ P) {
-  extern __shared__ __attribute__((aligned(16))) uint4 L[];
-  const int g = blockIdx.x;
-  const int64_t j0 = (int64_t)blockIdx.y * kFxE;
-  const int p0 = gtab[g], p1 = gtab[g + 1];
-  const int lo = gtab[NG + 1 + 2 * g], hi = gtab[NG + 2 + 2 * g];
-  const int W = kFxE + hi - lo;
-  // a block whose rows lie inside [0, nR) and whose samples inside [0, N)
-  // (every block but the segment's edges) loads without per-sample tests
-  const int64_t s_lo = base + j0 + lo, s_hi = s_lo + W - 1 + 7 * Qs;
-  const bool inner = j0 + lo >= 0 && j0 + lo + W <= nR && s_lo >= 0 && s_hi < N;
-  for (int k = 0; k < FXG; ++k) {
-    const int c = g * FXG + k;
-    const uint32_t pv = (pad_mode == PDD_PAD_VALUE) ? (uint32_t)padvals[c] : 0u;
+};
+// ... or straight from the input (no image R in HBM): each row element is
+// built the way k_interleave would -- S samples X(c, base + i + m*Qs) with the
+// reference pads (value / rotate).  Saves the image's write and read, and the
+// interleave launch, per segment (the per-rank work of a DM-sharded step that
+// does not shrink with the world size).  Integer input gives u16 eighths;
+// float32 input the float32 QUARTERS, each pattern element the float sum of
+// its group's fx elements in channel order (x_c0 + x_c0+1 [+ x_c0+2 +
+// x_c0+3]); the sweep then adds pattern series instead of channels -- the
+// reference's float64 channel sum regrouped, within the float32 parity bar
+// (and exact for integer-valued data).
+template <typename InT>
+struct FxFromInput {
+  static constexpr bool kF32 = std::is_same<InT, float>::value;
+  using El = typename std::conditional<kF32, ElemF32, ElemU16>::type;
+  using V = typename El::value_t;
+  static constexpr int kBlock = kF32 ? kFxEf : kFxE;
+  // non-temporal: the pattern image is read back only after the whole
+  // stage (12.6 against 13.0 ms per configs[3] launch, same box; the
+  // float32 stage 1 measured 8.6 ms with it against 7.5 without, on
+  // another box, so it keeps plain stores)
+  static constexpr bool kNontemporal = !kF32;
+  const SrcRows<InT> src;
+  const FxS1Args& a;
+  __device__ __forceinline__ explicit FxFromInput(const FxS1Args& a_) : src(a_.x, a_.lay), a(a_) {}
+  __device__ __forceinline__ void load_row(typename El::elem_t* L, int c, int64_t i0, int W) const {
+    const V pv = pad_value<V>(a.pad_mode, a.padvals, c);
+    // a block whose rows lie inside [0, nR) and whose samples inside [0, N)
+    // (every block but the segment's edges) loads without per-sample tests
+    const int64_t s_lo = a.base + i0, s_hi = s_lo + W - 1 + (El::S - 1) * a.Qs;
+    const bool inner = i0 >= 0 && i0 + W <= a.nR && s_lo >= 0 && s_hi < a.N;
     if (inner) {
       for (int e = threadIdx.x; e < W; e += 256) {
-        const int64_t sm = s_lo + e;
-        uint32_t v[8];
+        V v[El::S];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) v[m] = x[lay.at(c, sm + m * Qs)];
-        L[k * W + e] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16),
-                                  v[6] | (v[7] << 16));
+        for (int m = 0; m < El::S; ++m) v[m] = (V)src.at(c, s_lo + e + m * a.Qs);
+        L[e] = El::pack(v);
       }
-      continue;
+      return;
     }
     for (int e = threadIdx.x; e < W; e += 256) {
-      const int64_t i = j0 + lo + e;
-      uint32_t v[8];
+      const int64_t i = i0 + e;
+      V v[El::S];
 #pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const int64_t sm = base + i + m * Qs;
-        if (i < 0 || i >= nR) v[m] = 0u;
-        else if (sm >= 0 && sm < N) v[m] = x[lay.at(c, sm)];
-        else if (pad_mode == PDD_PAD_ROTATE) v[m] = x[lay.at(c, wrap_mod(sm, N))];
-        else v[m] = pv;
+      for (int m = 0; m < El::S; ++m) {
+        const int64_t sm = a.base + i + m * a.Qs;
+        v[m] = (i < 0 || i >= a.nR) ? (V)0 : padded_sample<V>(src, c, sm, a.N, a.pad_mode, pv);
       }
-      L[k * W + e] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16),
-                                v[6] | (v[7] << 16));
+      L[e] = El::pack(v);
     }
   }
-  __syncthreads();
-  const int* rng = gtab + 3 * NG + 1;
-  for (int pb = p0; pb < p1; pb += 64) {
-    const FxBatch B = fx_batch(pat, rng, pb, p1);
-    for (int i = 0; i < min(64, p1 - pb); ++i) {
-      const int p = pb + i;
-      const int4 q = make_int4(0, __builtin_amdgcn_readlane(B.y, i), __builtin_amdgcn_readlane(B.z, i),
-                               __builtin_amdgcn_readlane(B.w, i));
-      const int64_t jlo = __builtin_amdgcn_readlane(B.lo, i), jhi = nR + __builtin_amdgcn_readlane(B.hi, i);
-      if (j0 >= jhi || j0 + kFxE <= jlo) continue;  // no trial of p reads this block
-#pragma unroll
-      for (int e = threadIdx.x; e < kFxE; e += 256) {
-        const int64_t j = j0 + e;
-        if (j >= nR) break;  // (a block's elements outside [jlo, jhi): written, unread)
-        const uint4 a = L[e - lo], b = L[W + e - lo + q.y];
-        const uint4 c = FXG > 2 ? L[2 * W + e - lo + q.z] : make_uint4(0u, 0u, 0u, 0u);
-        const uint4 d = FXG > 3 ? L[3 * W + e - lo + q.w] : make_uint4(0u, 0u, 0u, 0u);
-        // non-temporal: the pattern image is read back only after the whole
-        // stage (12.6 against 13.0 ms per configs[3] launch, same box; the
-        // float32 stage 1 measured 8.6 ms with it against 7.5 without, on
-        // another box, so it keeps plain stores)
-        typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
-        const u32x4v sv = {a.x + b.x + c.x + d.x, a.y + b.y + c.y + d.y, a.z + b.z + c.z + d.z,
-                           a.w + b.w + c.w + d.w};
-        __builtin_nontemporal_store(sv, reinterpret_cast<u32x4v*>(P + (int64_t)p * nR + j));
-      }
-    }
-  }
-}
+};
 
-// Stage 1 of factorised float32 sweeps: the same from float32 rows into the
-// float32 QUARTERS image of k_interleave (element = 4 samples X(c, base + i +
-// m*Qs), m < 4), each pattern element the float sum of its group's fx
-// elements in channel order (x_c0 + x_c0+1 [+ x_c0+2 + x_c0+3]); the sweep
-// then adds pattern series instead of channels -- the reference's float64
-// channel sum regrouped, within the float32 parity bar (and exact for
-// integer-valued data).  Pads as k_interleave: value (per channel) / rotate.
-template <int FXG>
-__global__ __launch_bounds__(256) void k_fx_patterns_xf(const float* __restrict__ x, InLayout lay,
-                                                        int64_t N, int64_t base, int64_t Qs,
-                                                        int64_t nR, int pad_mode,
-                                                        const float* __restrict__ padvals,
-                                                        const int4* __restrict__ pat,
-                                                        const int* __restrict__ gtab, int NG, int fx,
-                                                        float4* __restrict__ P) {
-  extern __shared__ __attribute__((aligned(16))) float4 Lf[];
+// Stage 1 through LDS: load the group's FXG rows (Src), then write every
+// pattern of the group from them: pattern element j = the sum of the rows'
+// elements at j + r_k, in channel order ((a + b) + c) + d.
+template <typename Src, int FXG>
+__global__ __launch_bounds__(256) void k_fx_stage1(const FxS1Args a) {
+  using El = typename Src::El;
+  using E = typename El::elem_t;
+  constexpr int kE = Src::kBlock;
+  extern __shared__ __attribute__((aligned(16))) unsigned char fx_smem[];
+  E* L = reinterpret_cast<E*>(fx_smem);
+  const int* __restrict__ gtab = a.gtab;
+  const int4* __restrict__ pat = a.pat;
+  E* __restrict__ P = static_cast<E*>(a.R);
+  const int64_t nR = a.nR;
+  const int NG = a.NG;
   const int g = blockIdx.x;
-  const int64_t j0 = (int64_t)blockIdx.y * kFxEf;
+  const int64_t j0 = (int64_t)blockIdx.y * kE;
   const int p0 = gtab[g], p1 = gtab[g + 1];
   const int lo = gtab[NG + 1 + 2 * g], hi = gtab[NG + 2 + 2 * g];
-  const int W = kFxEf + hi - lo;
-  // interior blocks load without per-sample tests (as k_fx_patterns_x)
-  const int64_t s_lo = base + j0 + lo, s_hi = s_lo + W - 1 + 3 * Qs;
-  const bool inner = j0 + lo >= 0 && j0 + lo + W <= nR && s_lo >= 0 && s_hi < N;
-  for (int k = 0; k < FXG; ++k) {
-    const int c = g * FXG + k;
-    const float pv = (pad_mode == PDD_PAD_VALUE) ? padvals[c] : 0.f;
-    if (inner) {
-      for (int e = threadIdx.x; e < W; e += 256) {
-        const int64_t sm = s_lo + e;
-        Lf[k * W + e] = make_float4(x[lay.at(c, sm)], x[lay.at(c, sm + Qs)], x[lay.at(c, sm + 2 * Qs)],
-                                    x[lay.at(c, sm + 3 * Qs)]);
-      }
-      continue;
-    }
-    for (int e = threadIdx.x; e < W; e += 256) {
-      const int64_t i = j0 + lo + e;
-      float v[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int64_t sm = base + i + m * Qs;
-        if (i < 0 || i >= nR) v[m] = 0.f;
-        else if (sm >= 0 && sm < N) v[m] = x[lay.at(c, sm)];
-        else if (pad_mode == PDD_PAD_ROTATE) v[m] = x[lay.at(c, wrap_mod(sm, N))];
-        else v[m] = pv;
-      }
-      Lf[k * W + e] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
+  const int W = kE + hi - lo;
+  const Src src(a);
+  for (int k = 0; k < FXG; ++k) src.load_row(L + k * W, g * FXG + k, j0 + lo, W);
   __syncthreads();
   const int* rng = gtab + 3 * NG + 1;
   for (int pb = p0; pb < p1; pb += 64) {
@@ -896,24 +843,45 @@ __global__ __launch_bounds__(256) void k_fx_patterns_xf(const float* __restrict_
       const int4 q = make_int4(0, __builtin_amdgcn_readlane(B.y, i), __builtin_amdgcn_readlane(B.z, i),
                                __builtin_amdgcn_readlane(B.w, i));
       const int64_t jlo = __builtin_amdgcn_readlane(B.lo, i), jhi = nR + __builtin_amdgcn_readlane(B.hi, i);
-      if (j0 >= jhi || j0 + kFxEf <= jlo) continue;  // (as k_fx_patterns_lds)
+      if (j0 >= jhi || j0 + kE <= jlo) continue;  // no trial of p reads this block
 #pragma unroll
-      for (int e = threadIdx.x; e < kFxEf; e += 256) {
+      for (int e = threadIdx.x; e < kE; e += 256) {
         const int64_t j = j0 + e;
         if (j >= nR) break;  // (a block's elements outside [jlo, jhi): written, unread)
-        float4 s = Lf[e - lo];
-        const float4 b = Lf[W + e - lo + q.y];
-        s.x += b.x; s.y += b.y; s.z += b.z; s.w += b.w;
+        E s = El::add(L[e - lo], L[W + e - lo + q.y]);
         if constexpr (FXG > 2) {
-          const float4 c = Lf[2 * W + e - lo + q.z], d = Lf[3 * W + e - lo + q.w];
-          s.x += c.x; s.y += c.y; s.z += c.z; s.w += c.w;
-          s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
+          s = El::add(s, L[2 * W + e - lo + q.z]);
+          s = El::add(s, L[3 * W + e - lo + q.w]);
         }
-        P[(int64_t)p * nR + j] = s;
+        E* dst = P + (int64_t)p * nR + j;
+        if constexpr (Src::kNontemporal) {
+          typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
+          const u32x4v sv = {s.x, s.y, s.z, s.w};
+          __builtin_nontemporal_store(sv, reinterpret_cast<u32x4v*>(dst));
+        } else {
+          *dst = s;
+        }
       }
     }
   }
 }
+
+// Every LDS stage-1 instance (groups of 2 or 4: fx_build makes no others):
+// (source, group size) -> kernel.  src: the plan's dtype when stage 1 reads
+// the input, kFxImage when it reads a pre-pass image.
+typedef void (*fx_s1_fn)(FxS1Args);
+constexpr int kFxImage = -1;
+struct FxS1Instance {
+  int src, fx;
+  fx_s1_fn fn;
+  int block;  // elements per workgroup (the source's kBlock)
+};
+#define PDD_FX_S1(SRC_, ...) \
+  {SRC_, 2, k_fx_stage1<__VA_ARGS__, 2>, __VA_ARGS__::kBlock}, {SRC_, 4, k_fx_stage1<__VA_ARGS__, 4>, __VA_ARGS__::kBlock}
+static const FxS1Instance kFxS1Instances[] = {
+    PDD_FX_S1(kFxImage, FxFromImage), PDD_FX_S1(PDD_U8, FxFromInput<uint8_t>),
+    PDD_FX_S1(PDD_U16, FxFromInput<uint16_t>), PDD_FX_S1(PDD_F32, FxFromInput<float>)};
+#undef PDD_FX_S1
 
 // A whole window from ONE wave: runs of up to four consecutive 1 KiB DMAs
 // share one M0 value, the instruction offset (0 / 1024 / 2048 / 3072 bytes)
@@ -1688,11 +1656,31 @@ static void il_lohi(const pdd_sweep_plan* p, int64_t& lo, int64_t& hi) {
   }
 }
 
+// Geometry of a segment of cnt output columns: eighth / quarter length Qs
+// (whole tiles of Tq elements), nR = Qs + margin elements per image row
+// (margin: the delay span and one wave of slack), n_tblk time tiles.  The
+// one place it is derived: a caller's pattern buffer is sized
+// (pdd_sweep_pattern_bytes) by what execute_il checks it against.  Qs_pre:
+// the image was built by the previous sweep with that geometry (IlExtra).
+struct IlSeg {
+  int64_t lo, hi, margin, Qs, nR, n_tblk;
+};
+static IlSeg il_seg(const pdd_sweep_plan* p, int64_t cnt, int64_t Qs_pre = 0, int64_t nR_pre = 0) {
+  const int Tq = 64 * p->v.G;
+  IlSeg g;
+  il_lohi(p, g.lo, g.hi);
+  g.margin = (g.hi - g.lo) + 64;
+  g.Qs = Qs_pre ? Qs_pre : cdiv(cdiv(cnt, p->v.S), Tq) * Tq;
+  g.nR = Qs_pre ? nR_pre : g.Qs + g.margin;
+  // (delay-aligned factorised tiles: fx_tpad / Tq more time tiles, whose
+  // trials cover the columns their skew moved past the last tile)
+  g.n_tblk = g.Qs / Tq + (p->fx ? p->fx_tpad / Tq : 0);
+  return g;
+}
+
 static int64_t il_seg_samples(const pdd_sweep_plan* p, hipStream_t st) {
   const int Tq = 64 * p->v.G;
   const int64_t C = p->C * p->n_grp;
-  int64_t lo, hi;
-  il_lohi(p, lo, hi);
   // bytes of R per segment: 16 GiB = one segment per quarter of a 4096 x
   // 2^22 block (configs[3] at 4 time batches), few launches per step
   int64_t budget = (int64_t)16 << 30;
@@ -1717,7 +1705,7 @@ static int64_t il_seg_samples(const pdd_sweep_plan* p, hipStream_t st) {
     }
   }
   const int64_t nr_max = budget / (rows * 16);
-  return (nr_max - (hi - lo) - 64) / Tq * Tq * p->v.S;
+  return (nr_max - il_seg(p, 0).margin) / Tq * Tq * p->v.S;
 }
 
 struct IlExtra {
@@ -1734,11 +1722,123 @@ struct IlExtra {
   uint4* P_ext = nullptr;
   int64_t P_bytes = 0;
 };
+
+// One execute of the interleaved path: what the three parts of a segment
+// (image, patterns, sweep) share.
+struct IlRun {
+  const pdd_sweep_plan* p;
+  const void* x;
+  int64_t N;
+  InLayout lay;
+  int64_t x_off;
+  int pad_mode;
+  const float* padvals;
+  const IlExtra& ex;
+  hipStream_t st;
+  // factorised plans with the LDS stage 1 build their pattern image straight
+  // from x (FxFromInput): no u16-eighths image R
+  bool fx_direct;
+  float4* R;  // C rows of the image + one row of zeros (the u16 kernel's pad channel)
+  uint4* P;   // factorised plans: the pattern image (stage 1), n_pat rows + a row of zeros
+};
+
+static int il_launch_failed() {
+  set_error("pdd_sweep_execute: kernel launch failed");
+  return -3;
+}
+
+// Part 1: the segment's image by the pre-pass (r.R == nullptr: built by the
+// previous sweep / none, factorised stage 1 reads x).
+static int il_build_image(const IlRun& r, const IlSeg& g, int64_t t_base) {
+  const pdd_sweep_plan* p = r.p;
+  if (!r.R) return 0;
+  const int64_t C = p->C * p->n_grp;
+  if (hipMemsetAsync(r.R + C * g.nR, 0, (size_t)g.nR * sizeof(float4), r.st) != hipSuccess)
+    return il_launch_failed();
+  const int ds = r.ex.ds;
+  const int64_t b0 = t_base + g.lo + r.x_off;
+  int vec = 0;
+  if (ds == 2 || ds == 4) {
+    const int J = 16 / ds;
+    if ((uintptr_t)r.x % 16 == 0 && r.lay.ld % 16 == 0 && b0 % J == 0 && g.Qs % J == 0) vec = 16;
+    else if ((uintptr_t)r.x % ds == 0 && r.lay.ld % ds == 0) vec = 1;
+  }
+  for (const IlInstance& k : kIlInstances) {
+    if (k.ds != ds || k.vec != vec || k.dtype != p->dtype || k.u16 != (p->v.S == 8)) continue;
+    const IlArgs a{r.x, r.lay, r.N, b0, g.Qs, g.nR, r.pad_mode, r.padvals, r.R};
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)cdiv(g.nR, k.per_block), (unsigned)C), dim3(256), 0,
+                       r.st, a);
+    return hipGetLastError() == hipSuccess ? 0 : il_launch_failed();
+  }
+  set_error("pdd_sweep_execute: no pre-pass kernel (downsample %d, dtype %d)", ds, p->dtype);
+  return -3;
+}
+
+// Part 2 (factorised plans): the segment's pattern image by stage 1.
+static int il_build_patterns(const IlRun& r, const IlSeg& g, int64_t t_base) {
+  const pdd_sweep_plan* p = r.p;
+  // pdd_sweep_plan_set_poison (a parity-test switch): the pattern rows
+  // are filled with 0xFF bytes first, so a sum that read an element stage
+  // 1 did not write (the per-pattern ranges of fx_build) shows as a NaN /
+  // an overflowed lane instead of a stale-but-plausible value
+  if (p->poison &&
+      hipMemsetAsync(r.P, 0xFF, (size_t)(p->n_pat * g.nR) * sizeof(uint4), r.st) != hipSuccess)
+    return il_launch_failed();
+  if (hipMemsetAsync(r.P + p->n_pat * g.nR, 0, (size_t)g.nR * sizeof(uint4), r.st) != hipSuccess)
+    return il_launch_failed();
+  if (!p->d_gtab) {
+    // (a group's relative shifts span more than kFxRspan: the plain stage 1)
+    hipLaunchKernelGGL(k_fx_patterns, dim3((unsigned)p->n_pat, (unsigned)cdiv(g.nR, 256 * kIlPer)),
+                       dim3(256), 0, r.st, (const uint4*)r.R, g.nR, (const int4*)p->d_pat, p->fx, r.P);
+    return hipGetLastError() == hipSuccess ? 0 : il_launch_failed();
+  }
+  for (const FxS1Instance& k : kFxS1Instances) {
+    if (k.src != (r.fx_direct ? p->dtype : kFxImage) || k.fx != p->fx) continue;
+    const int NG = (int)(p->C / p->fx);
+    const FxS1Args a{{r.fx_direct ? r.x : r.R, r.lay, r.N, t_base + g.lo + r.x_off, g.Qs, g.nR,
+                      r.pad_mode, r.padvals, r.P},
+                     (const int4*)p->d_pat, p->d_gtab, NG};
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)NG, (unsigned)cdiv(g.nR, k.block)), dim3(256),
+                       (size_t)(p->fx * (k.block + p->fx_rspan)) * sizeof(uint4), r.st, a);
+    return hipGetLastError() == hipSuccess ? 0 : il_launch_failed();
+  }
+  set_error("pdd_sweep_execute: no stage-1 kernel (groups of %d, dtype %d)", p->fx, p->dtype);
+  return -3;
+}
+
+// Part 3: the sweep of the segment's cnt columns from t_base on, between
+// the plan's timing events.
+static int il_launch_sweep(const IlRun& r, const IlSeg& g, int64_t t_base, int64_t cnt, float* out,
+                           int64_t ld_out, int64_t row_g, int64_t row_d, float out_bias, int flush_n) {
+  const pdd_sweep_plan* p = r.p;
+  const IlExtra& ex = r.ex;
+  const int64_t blocks = g.n_tblk * p->n_dblk * p->n_grp;
+  if (blocks >= (1ll << 31)) {
+    set_error("pdd_sweep_execute: grid too large");
+    return -1;
+  }
+  pdd_sweep_plan* pm = const_cast<pdd_sweep_plan*>(p);
+  const bool bracket = p->timing && p->timed < pdd_sweep_plan::kEvPairs;
+  if (p->timing && !bracket) pm->dropped++;
+  if (bracket) (void)hipEventRecord(p->ev[2 * p->timed], r.st);
+  hipLaunchKernelGGL(il_kernel_for(p->v, p->fx != 0), dim3((unsigned)blocks), dim3(p->v.threads()),
+                     p->lds_bytes, r.st, ex.R_pre ? ex.R_pre : (p->fx ? (const float4*)r.P : r.R),
+                     g.nR, (int)(p->fx ? p->fx_rows - 1 : p->C), (int)g.lo, p->d_tab, p->d_bmin,
+                     p->maxch, out, ld_out, (int)p->D, g.Qs, t_base, t_base + cnt, p->stride,
+                     (int)g.n_tblk, (int)p->n_dblk, debug_flags(), row_g, row_d, flush_n, out_bias,
+                     ex.r2_pad, ex.r2_nR, ex.r2_ov, (const int4*)p->d_wt, p->d_sig);
+  const int rc = hipGetLastError() == hipSuccess ? 0 : il_launch_failed();
+  if (bracket) {
+    (void)hipEventRecord(p->ev[2 * p->timed + 1], r.st);
+    pm->timed++;
+  }
+  return rc;
+}
+
 static int execute_il(const pdd_sweep_plan* p, const void* x, int64_t N, InLayout lay,
                       int64_t x_off, int pad_mode, const float* padvals, float* out,
                       int64_t ld_out, int64_t n_out, int64_t row_g, int64_t row_d, float out_bias,
                       void* stream, const IlExtra& ex = IlExtra()) {
-  const int ds = ex.ds;
   const int Tq = 64 * p->v.G;
   const int SP = p->v.S;  // samples per element: 4 (float32 quarters) or 8 (u16 eighths)
   const bool u16 = (SP == 8);
@@ -1752,174 +1852,55 @@ static int execute_il(const pdd_sweep_plan* p, const void* x, int64_t N, InLayou
   PDD_REQUIRE(!u16 || flush_n >= p->v.CC, "pdd_sweep_execute: input bound %d too large for the "
               "packed 16-bit sums", vmax);
   const int64_t C = p->C * p->n_grp;  // all channels (groups are contiguous channel ranges)
-  int64_t lo, hi;
-  il_lohi(p, lo, hi);
+  hipStream_t st = as_stream(stream);
   // output samples per segment
-  int64_t seg = (ex.one_seg || ex.P_ext) ? std::max<int64_t>(n_out, 1)
-                                         : il_seg_samples(p, as_stream(stream));
+  int64_t seg = (ex.one_seg || ex.P_ext) ? std::max<int64_t>(n_out, 1) : il_seg_samples(p, st);
+  IlSeg ga = il_seg(p, 0);
   PDD_REQUIRE(seg > 0, "pdd_sweep_execute: delay span %lld too wide for the segment budget",
-              (long long)(hi - lo));
+              (long long)(ga.hi - ga.lo));
   // equal segments (whole tiles): every launch does the same work
-  const int64_t tile_s = (int64_t)SP * Tq;
   const int64_t nseg = cdiv(n_out, seg);
-  seg = cdiv(cdiv(n_out, nseg), tile_s) * tile_s;
-  const int64_t qs_max = seg / SP;
-  const int64_t nr_alloc = qs_max + (hi - lo) + 64;
+  seg = cdiv(cdiv(n_out, nseg), (int64_t)SP * Tq) * SP * Tq;
+  ga = il_seg(p, seg);  // the longest segment: scratch is sized by it
   PDD_REQUIRE(!(ex.r2_pad || ex.R_pre) || nseg == 1,
               "pdd_subband_chain: the stages need one segment each (%lld)", (long long)nseg);
   if (ex.R_pre)
-    PDD_REQUIRE(lo == 0 && n_out <= SP * ex.Qs_pre && ex.Qs_pre % Tq == 0 &&
-                    ex.nR_pre >= ex.Qs_pre + hi + 64 && !u16,
+    PDD_REQUIRE(ga.lo == 0 && n_out <= SP * ex.Qs_pre && ex.Qs_pre % Tq == 0 &&
+                    ex.nR_pre >= ex.Qs_pre + ga.hi + 64 && !u16,
                 "pdd_subband_chain: stage-2 image does not cover this plan");
-  float4* R = nullptr;
-  hipStream_t st = as_stream(stream);
-  // factorised plans with the LDS stage 1 build their pattern image straight
-  // from x (k_fx_patterns_x): no u16-eighths image R
-  const bool fx_direct = p->fx && p->d_gtab && !ex.R_pre && ds == 1;
-  // C rows of the image + one row of zeros (the u16 kernel's pad channel)
-  if (!ex.R_pre && !fx_direct) {
-    R = static_cast<float4*>(scratch(st, kScratchImage, (size_t)((C + 1) * nr_alloc) * sizeof(float4)));
-    if (!R) return -2;
+  IlRun r{p, x, N, lay, x_off, pad_mode, padvals, ex, st,
+          p->fx && p->d_gtab && !ex.R_pre && ex.ds == 1, nullptr, ex.P_ext};
+  if (!ex.R_pre && !r.fx_direct) {
+    r.R = static_cast<float4*>(scratch(st, kScratchImage, (size_t)((C + 1) * ga.nR) * sizeof(float4)));
+    if (!r.R) return -2;
   }
-  // factorised plans: the pattern image (stage 1), n_pat rows + a row of zeros
-  uint4* P = nullptr;
-  if (ex.P_ext) {
-    PDD_REQUIRE(p->fx && (int64_t)(p->n_pat + 1) * nr_alloc * 16 <= ex.P_bytes,
+  if (ex.P_ext)
+    PDD_REQUIRE(p->fx && (int64_t)(p->n_pat + 1) * ga.nR * 16 <= ex.P_bytes,
                 "pdd_sweep_execute_stage: pattern buffer of %lld bytes < %lld",
-                (long long)ex.P_bytes, (long long)((p->n_pat + 1) * nr_alloc * 16));
-    P = ex.P_ext;
-  }
+                (long long)ex.P_bytes, (long long)((p->n_pat + 1) * ga.nR * 16));
   if (p->fx) {
     // (ds > 1: the interleave pre-pass co-adds the raw rows into R and stage
     // 1 builds the patterns from R: sums of fx co-adds <= 4 * 1020 stay exact)
     PDD_REQUIRE(u16 == (p->dtype != PDD_F32) && !ex.r2_pad && !ex.R_pre && p->n_grp == 1 &&
-                    (u16 || fx_direct),
+                    (u16 || r.fx_direct),
                 "pdd_sweep_execute: factorised plans take single-group input (float32: raw rate)");
-    if (!P)
-      P = static_cast<uint4*>(scratch(st, kScratchPattern, (size_t)((p->n_pat + 1) * nr_alloc) * sizeof(uint4)));
-    if (!P) return -2;
+    if (!r.P)
+      r.P = static_cast<uint4*>(scratch(st, kScratchPattern, (size_t)((p->n_pat + 1) * ga.nR) * sizeof(uint4)));
+    if (!r.P) return -2;
   }
-  const int dbg = debug_flags();
   int rc = 0;
   for (int64_t t_base = 0; t_base < n_out && rc == 0; t_base += seg) {
     const int64_t cnt = std::min(seg, n_out - t_base);
-    const int64_t Qs = ex.R_pre ? ex.Qs_pre : cdiv(cdiv(cnt, SP), Tq) * Tq;
-    const int64_t nR = ex.R_pre ? ex.nR_pre : Qs + (hi - lo) + 64;
-    if (ex.r2_pad && ex.r2_nR != 2 * Qs + ex.r2_ov) { rc = -4; break; }
-    dim3 g1((unsigned)cdiv(nR, 256 * kIlPer), (unsigned)C);
-    if (ex.R_pre || fx_direct) {
-      // image built by the previous sweep / none (factorised stage 1 reads x)
-    } else if (hipMemsetAsync(R + C * nR, 0, (size_t)nR * sizeof(float4), st) != hipSuccess) {
-      rc = -3;
-      break;
-    } else if (ds > 1) {
-      const bool vec = ds != 3 && (uintptr_t)x % ds == 0 && lay.ld % ds == 0;
-      const int64_t b0 = t_base + lo + x_off;
-      const int J = 16 / (int)ds;
-      const bool vec16 = ds != 3 && (uintptr_t)x % 16 == 0 && lay.ld % 16 == 0 && b0 % J == 0 &&
-                         Qs % J == 0;
-      const dim3 gv((unsigned)cdiv(nR, 256 * J), (unsigned)C);
-#define ILDS(F_, V_)                                                                           \
-  hipLaunchKernelGGL((k_interleave_u16_ds<F_, V_>), g1, dim3(256), 0, st, (const uint8_t*)x, \
-                     lay.ld, N, b0, Qs, nR, pad_mode, padvals, (uint4*)R)
-      if (vec16 && ds == 2)
-        hipLaunchKernelGGL(k_interleave_u16_ds_v<2>, gv, dim3(256), 0, st, (const uint8_t*)x,
-                           lay.ld, N, b0, Qs, nR, pad_mode, padvals, (uint4*)R);
-      else if (vec16)
-        hipLaunchKernelGGL(k_interleave_u16_ds_v<4>, gv, dim3(256), 0, st, (const uint8_t*)x,
-                           lay.ld, N, b0, Qs, nR, pad_mode, padvals, (uint4*)R);
-      else if (ds == 2 && vec) ILDS(2, true);
-      else if (ds == 2) ILDS(2, false);
-      else if (ds == 3) ILDS(3, false);
-      else if (vec) ILDS(4, true);
-      else ILDS(4, false);
-#undef ILDS
-    } else if (u16 && p->dtype == PDD_U8)
-      hipLaunchKernelGGL(k_interleave_u16<uint8_t>, g1, dim3(256), 0, st, (const uint8_t*)x, lay, N,
-                         t_base + lo + x_off, Qs, nR, pad_mode, padvals, (uint4*)R);
-    else if (u16)
-      hipLaunchKernelGGL(k_interleave_u16<uint16_t>, g1, dim3(256), 0, st, (const uint16_t*)x, lay,
-                         N, t_base + lo + x_off, Qs, nR, pad_mode, padvals, (uint4*)R);
-    else if (p->dtype == PDD_U16)
-      hipLaunchKernelGGL(k_interleave<uint16_t>, g1, dim3(256), 0, st, (const uint16_t*)x, lay, N,
-                         t_base + lo + x_off, Qs, nR, pad_mode, padvals, R);
-    else if (p->dtype == PDD_U8)
-      hipLaunchKernelGGL(k_interleave<uint8_t>, g1, dim3(256), 0, st, (const uint8_t*)x, lay, N,
-                         t_base + lo + x_off, Qs, nR, pad_mode, padvals, R);
-    else
-      hipLaunchKernelGGL(k_interleave<float>, g1, dim3(256), 0, st, (const float*)x, lay, N,
-                         t_base + lo + x_off, Qs, nR, pad_mode, padvals, R);
-    if (hipGetLastError() != hipSuccess) { rc = -3; break; }
-    if (p->fx && (ex.stages & 1)) {
-      // pdd_sweep_plan_set_poison (a parity-test switch): the pattern rows
-      // are filled with 0xFF bytes first, so a sum that read an element stage
-      // 1 did not write (the per-pattern ranges of fx_build) shows as a NaN /
-      // an overflowed lane instead of a stale-but-plausible value
-      if (p->poison && hipMemsetAsync(P, 0xFF, (size_t)(p->n_pat * nR) * sizeof(uint4), st) != hipSuccess) {
-        rc = -3;
-        break;
-      }
-      if (hipMemsetAsync(P + p->n_pat * nR, 0, (size_t)nR * sizeof(uint4), st) != hipSuccess) {
-        rc = -3;
-        break;
-      }
-      const int NG = (int)(p->C / p->fx);
-      const int fxe = p->dtype == PDD_F32 ? kFxEf : kFxE;  // stage-1 block length
-      const dim3 gp((unsigned)NG, (unsigned)cdiv(nR, fxe));
-      const size_t lds_p = (size_t)(p->fx * (fxe + p->fx_rspan)) * sizeof(uint4);
-      const int64_t b0 = t_base + lo + x_off;
-      // (stage-1 kernels are instanced per group size: fx_build makes groups of 2 or 4)
-#define PDD_FX_S1(K2, K4, ...)                                                     \
-  do {                                                                             \
-    if (p->fx == 4) hipLaunchKernelGGL(K4, gp, dim3(256), lds_p, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL(K2, gp, dim3(256), lds_p, st, __VA_ARGS__);            \
-  } while (0)
-      if (fx_direct && p->dtype == PDD_F32) {
-        PDD_FX_S1(k_fx_patterns_xf<2>, k_fx_patterns_xf<4>, (const float*)x, lay, N, b0, Qs, nR,
-                  pad_mode, padvals, (const int4*)p->d_pat, p->d_gtab, NG, p->fx, (float4*)P);
-      } else if (fx_direct && p->dtype == PDD_U8) {
-        PDD_FX_S1((k_fx_patterns_x<uint8_t, 2>), (k_fx_patterns_x<uint8_t, 4>), (const uint8_t*)x,
-                  lay, N, b0, Qs, nR, pad_mode, padvals, (const int4*)p->d_pat, p->d_gtab, NG, p->fx,
-                  P);
-      } else if (fx_direct) {
-        PDD_FX_S1((k_fx_patterns_x<uint16_t, 2>), (k_fx_patterns_x<uint16_t, 4>), (const uint16_t*)x,
-                  lay, N, b0, Qs, nR, pad_mode, padvals, (const int4*)p->d_pat, p->d_gtab, NG, p->fx,
-                  P);
-#undef PDD_FX_S1
-      } else if (p->d_gtab) {
-        hipLaunchKernelGGL(k_fx_patterns_lds, gp, dim3(256), lds_p, st, (const uint4*)R, nR,
-                           (const int4*)p->d_pat, p->d_gtab, NG, p->fx, P);
-      } else {
-        hipLaunchKernelGGL(k_fx_patterns, dim3((unsigned)p->n_pat, (unsigned)cdiv(nR, 256 * kIlPer)),
-                           dim3(256), 0, st, (const uint4*)R, nR, (const int4*)p->d_pat, p->fx, P);
-      }
-      if (hipGetLastError() != hipSuccess) { rc = -3; break; }
+    const IlSeg g = il_seg(p, cnt, ex.R_pre ? ex.Qs_pre : 0, ex.nR_pre);
+    if (ex.r2_pad && ex.r2_nR != 2 * g.Qs + ex.r2_ov) {
+      set_error("pdd_subband_chain: stage-2 image geometry mismatch");
+      return -4;
     }
-    // (delay-aligned factorised tiles: fx_tpad / Tq more time tiles, whose
-    // trials cover the columns their skew moved past the last tile)
-    if (!(ex.stages & 2)) continue;  // (staged: stage 1 only)
-    const int64_t n_tblk = Qs / Tq + (p->fx ? p->fx_tpad / Tq : 0);
-    const int64_t blocks = n_tblk * p->n_dblk * p->n_grp;
-    if (blocks >= (1ll << 31)) { rc = -1; break; }
-    pdd_sweep_plan* pm = const_cast<pdd_sweep_plan*>(p);
-    const bool bracket = p->timing && p->timed < pdd_sweep_plan::kEvPairs;
-    if (p->timing && !bracket) pm->dropped++;
-    if (bracket) (void)hipEventRecord(p->ev[2 * p->timed], st);
-    hipLaunchKernelGGL(il_kernel_for(p->v, p->fx != 0), dim3((unsigned)blocks), dim3(p->v.threads()),
-                       p->lds_bytes, st, ex.R_pre ? ex.R_pre : (p->fx ? (const float4*)P : R), nR,
-                       (int)(p->fx ? p->fx_rows - 1 : p->C), (int)lo, p->d_tab,
-                       p->d_bmin, p->maxch, out, ld_out, (int)p->D, Qs, t_base, t_base + cnt,
-                       p->stride, (int)n_tblk, (int)p->n_dblk, dbg, row_g, row_d, flush_n, out_bias,
-                       ex.r2_pad, ex.r2_nR, ex.r2_ov, (const int4*)p->d_wt, p->d_sig);
-    if (hipGetLastError() != hipSuccess) rc = -3;
-    if (bracket) {
-      (void)hipEventRecord(p->ev[2 * p->timed + 1], st);
-      pm->timed++;
-    }
+    rc = il_build_image(r, g, t_base);
+    if (rc == 0 && p->fx && (ex.stages & 1)) rc = il_build_patterns(r, g, t_base);
+    if (rc == 0 && (ex.stages & 2))  // (staged: stage 1 only)
+      rc = il_launch_sweep(r, g, t_base, cnt, out, ld_out, row_g, row_d, out_bias, flush_n);
   }
-  if (rc == -4) set_error("pdd_subband_chain: stage-2 image geometry mismatch");
-  if (rc == -1) set_error("pdd_sweep_execute: grid too large");
-  if (rc == -3) set_error("pdd_sweep_execute: kernel launch failed");
   return rc;
 }
 
@@ -1953,13 +1934,9 @@ static int plan_create(const int32_t* host_table, int64_t n_grp, int64_t D, int6
   if (e == hipSuccess && !sp.fxt.gtab.empty()) {
     e = upload(&p->d_gtab, sp.fxt.gtab);
     // the LDS stage 1 (gtab: every group's shift range fits kFxRspan)
-    for (const void* kf :
-         {(const void*)k_fx_patterns_lds, (const void*)k_fx_patterns_x<uint8_t, 2>,
-          (const void*)k_fx_patterns_x<uint8_t, 4>, (const void*)k_fx_patterns_x<uint16_t, 2>,
-          (const void*)k_fx_patterns_x<uint16_t, 4>, (const void*)k_fx_patterns_xf<2>,
-          (const void*)k_fx_patterns_xf<4>})
+    for (const FxS1Instance& k : kFxS1Instances)
       if (e == hipSuccess)
-        e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(4 * (kFxEf + kFxRspan) * sizeof(uint4)));
   }
   if (e != hipSuccess) {
@@ -1979,6 +1956,34 @@ static int plan_create(const int32_t* host_table, int64_t n_grp, int64_t D, int6
   *plan_out = p;
   return 0;
 }
+
+// The shape, stride, piece and pad checks of the execute entry points (fn:
+// the entry point's name in the message).  N >= N_min samples per row, ld_min
+// apart at least (channel-major input); 0 <= n_out <= n_out_max columns.
+struct ExecShape {
+  const char* fn;
+  int64_t N, N_min, ld, ld_min, piece, x_off, n_out, n_out_max, ld_out, row_g, row_d;
+  int pad_mode;
+  const float* padvals;
+};
+static int check_execute(const ExecShape& a) {
+  PDD_REQUIRE(a.N >= a.N_min && a.n_out >= 0 && a.n_out <= a.n_out_max && a.ld_out >= a.n_out &&
+                  a.x_off >= 0 && a.row_g >= 0 && a.row_d >= 0,
+              "%s: bad shape", a.fn);
+  PDD_REQUIRE(a.piece > 0 || a.ld >= a.ld_min, "%s: row stride %lld < %lld", a.fn, (long long)a.ld,
+              (long long)a.ld_min);
+  PDD_REQUIRE(a.piece == 0 || (a.piece & (a.piece - 1)) == 0, "%s: piece must be 2^k", a.fn);
+  PDD_REQUIRE(a.pad_mode == PDD_PAD_ROTATE || (a.pad_mode == PDD_PAD_VALUE && a.padvals),
+              "%s: bad pad mode %d", a.fn, a.pad_mode);
+  return 0;
+}
+// Channel-major rows ld apart, or pieces of `piece` samples of C channels.
+static InLayout in_layout(int64_t ld, int64_t piece = 0, int64_t C = 0) {
+  InLayout lay{ld, piece, 0, C * piece};
+  while ((1ll << lay.psh) < piece) ++lay.psh;
+  return lay;
+}
+constexpr int64_t kAnyColumns = INT64_MAX;
 
 extern "C" {
 
@@ -2033,20 +2038,13 @@ int pdd_sweep_execute_ex(const pdd_sweep_plan* p, const void* x, int64_t N, int6
                          int64_t piece, int64_t x_off, int pad_mode, const float* padvals,
                          float* out, int64_t ld_out, int64_t n_out, float out_bias, void* stream) {
   PDD_REQUIRE(p && x && out, "pdd_sweep_execute: null pointer");
-  PDD_REQUIRE(N > 0 && n_out >= 0 && ld_out >= n_out && x_off >= 0, "pdd_sweep_execute: bad shape");
-  PDD_REQUIRE(piece > 0 || ld >= N, "pdd_sweep_execute: row stride %lld < N", (long long)ld);
-  PDD_REQUIRE(piece == 0 || (piece & (piece - 1)) == 0, "pdd_sweep_execute: piece must be 2^k");
-  PDD_REQUIRE(pad_mode == PDD_PAD_ROTATE || (pad_mode == PDD_PAD_VALUE && padvals),
-              "pdd_sweep_execute: bad pad mode %d", pad_mode);
+  if (int rc = check_execute({"pdd_sweep_execute", N, 1, ld, N, piece, x_off, n_out, kAnyColumns,
+                              ld_out, 0, 0, pad_mode, padvals}))
+    return rc;
   if (n_out == 0) return 0;
-  InLayout lay{ld, piece, 0, 0};
-  if (piece) {
-    while ((1ll << lay.psh) < piece) ++lay.psh;
-    lay.pstride = p->C * p->n_grp * piece;
-  }
   if (p->v.kind == 0)
-    return execute_il(p, x, N, lay, x_off, pad_mode, padvals, out, ld_out, n_out, 0, 1, out_bias,
-                      stream);
+    return execute_il(p, x, N, in_layout(ld, piece, p->C * p->n_grp), x_off, pad_mode, padvals, out,
+                      ld_out, n_out, 0, 1, out_bias, stream);
   PDD_REQUIRE(piece == 0 && x_off == 0 && out_bias == 0.f,
               "pdd_sweep_execute: the generic (sparse-grid) kernel reads channel-major input "
               "at offset 0 without an output bias");
@@ -2068,11 +2066,7 @@ int pdd_sweep_execute_ex(const pdd_sweep_plan* p, const void* x, int64_t N, int6
 int64_t pdd_sweep_pattern_bytes(const pdd_sweep_plan* p, int64_t n_out) {
   PDD_REQUIRE(p && n_out >= 0, "pdd_sweep_pattern_bytes: bad arguments");
   if (!p->fx || !p->d_gtab || p->v.kind != 0) return 0;
-  const int Tq = 64 * p->v.G;
-  int64_t lo, hi;
-  il_lohi(p, lo, hi);
-  const int64_t Qs = cdiv(cdiv(std::max<int64_t>(n_out, 1), p->v.S), Tq) * Tq;
-  return (int64_t)(p->n_pat + 1) * (Qs + (hi - lo) + 64) * 16;
+  return (int64_t)(p->n_pat + 1) * il_seg(p, std::max<int64_t>(n_out, 1)).nR * 16;
 }
 
 int pdd_sweep_execute_stage(const pdd_sweep_plan* p, const void* x, int64_t N, int64_t ld,
@@ -2083,24 +2077,17 @@ int pdd_sweep_execute_stage(const pdd_sweep_plan* p, const void* x, int64_t N, i
   PDD_REQUIRE(p->fx && p->d_gtab && p->v.kind == 0 && p->n_grp == 1,
               "pdd_sweep_execute_stage: needs a factorised single-group plan");
   PDD_REQUIRE(stage >= 1 && stage <= 3, "pdd_sweep_execute_stage: stage %d not 1, 2 or 3", stage);
-  PDD_REQUIRE(N > 0 && n_out >= 0 && (stage == 1 || ld_out >= n_out) && x_off >= 0,
-              "pdd_sweep_execute_stage: bad shape");
-  PDD_REQUIRE(piece > 0 || ld >= N, "pdd_sweep_execute_stage: row stride %lld < N", (long long)ld);
-  PDD_REQUIRE(piece == 0 || (piece & (piece - 1)) == 0, "pdd_sweep_execute_stage: piece must be 2^k");
-  PDD_REQUIRE(pad_mode == PDD_PAD_ROTATE || (pad_mode == PDD_PAD_VALUE && padvals),
-              "pdd_sweep_execute_stage: bad pad mode %d", pad_mode);
+  // (stage 1 alone writes no plane: no ld_out to check)
+  if (int rc = check_execute({"pdd_sweep_execute_stage", N, 1, ld, N, piece, x_off, n_out,
+                              kAnyColumns, stage == 1 ? n_out : ld_out, 0, 0, pad_mode, padvals}))
+    return rc;
   if (n_out == 0) return 0;
-  InLayout lay{ld, piece, 0, 0};
-  if (piece) {
-    while ((1ll << lay.psh) < piece) ++lay.psh;
-    lay.pstride = p->C * piece;
-  }
   IlExtra ex;
   ex.stages = stage;
   ex.P_ext = static_cast<uint4*>(patterns);
   ex.P_bytes = pattern_bytes;
-  return execute_il(p, x, N, lay, x_off, pad_mode, padvals, out, ld_out, n_out, 0, 1, out_bias,
-                    stream, ex);
+  return execute_il(p, x, N, in_layout(ld, piece, p->C), x_off, pad_mode, padvals, out, ld_out,
+                    n_out, 0, 1, out_bias, stream, ex);
 }
 
 int pdd_stream_create_cu_mask(const uint32_t* mask, int n_words, void** stream) {
@@ -2122,13 +2109,12 @@ int pdd_sweep_execute_grouped(const pdd_sweep_plan* p, const void* x, int64_t N,
                               int64_t n_out, int64_t row_g, int64_t row_d, void* stream) {
   PDD_REQUIRE(p && x && out, "pdd_sweep_execute_grouped: null pointer");
   PDD_REQUIRE(p->v.kind == 0, "pdd_sweep_execute_grouped: plan has no grouped kernel");
-  PDD_REQUIRE(N > 0 && ld >= N && n_out >= 0 && ld_out >= n_out && row_g >= 0 && row_d >= 0,
-              "pdd_sweep_execute_grouped: bad shape");
-  PDD_REQUIRE(pad_mode == PDD_PAD_ROTATE || (pad_mode == PDD_PAD_VALUE && padvals),
-              "pdd_sweep_execute_grouped: bad pad mode %d", pad_mode);
+  if (int rc = check_execute({"pdd_sweep_execute_grouped", N, 1, ld, N, 0, 0, n_out, kAnyColumns,
+                              ld_out, row_g, row_d, pad_mode, padvals}))
+    return rc;
   if (n_out == 0) return 0;
-  return execute_il(p, x, N, InLayout{ld, 0, 0, 0}, 0, pad_mode, padvals, out, ld_out, n_out, row_g,
-                    row_d, 0.f, stream);
+  return execute_il(p, x, N, in_layout(ld), 0, pad_mode, padvals, out, ld_out, n_out, row_g, row_d,
+                    0.f, stream);
 }
 
 int pdd_sweep_execute_ds(const pdd_sweep_plan* p, const uint8_t* x8, int64_t n_raw, int64_t ld,
@@ -2141,15 +2127,13 @@ int pdd_sweep_execute_ds(const pdd_sweep_plan* p, const uint8_t* x8, int64_t n_r
   PDD_REQUIRE(ds >= 2 && ds <= 4, "pdd_sweep_execute_ds: downsample factor %lld not in 2..4",
               (long long)ds);
   const int64_t N = n_raw / ds;
-  PDD_REQUIRE(N >= 0 && ld >= n_raw && n_out >= 0 && n_out <= N && ld_out >= n_out && row_g >= 0 &&
-                  row_d >= 0,
-              "pdd_sweep_execute_ds: bad shape");
-  PDD_REQUIRE(pad_mode == PDD_PAD_ROTATE || (pad_mode == PDD_PAD_VALUE && padvals),
-              "pdd_sweep_execute_ds: bad pad mode %d", pad_mode);
+  if (int rc = check_execute({"pdd_sweep_execute_ds", N, 0, ld, n_raw, 0, 0, n_out, N, ld_out, row_g,
+                              row_d, pad_mode, padvals}))
+    return rc;
   if (n_out == 0) return 0;
   IlExtra ex;
   ex.ds = (int)ds;
-  return execute_il(p, x8, N, InLayout{ld, 0, 0, 0}, 0, pad_mode, padvals, out, ld_out, n_out,
+  return execute_il(p, x8, N, in_layout(ld), 0, pad_mode, padvals, out, ld_out, n_out,
                     p->n_grp > 1 ? row_g : 0, row_d, 0.f, stream, ex);
 }
 
@@ -2167,12 +2151,10 @@ int pdd_subband_chain(const pdd_sweep_plan* p1, const void* x, int64_t n_raw, in
   PDD_REQUIRE(p2->C * p2->n_grp == p1->D * p1->n_grp,
               "pdd_subband_chain: stage-2 channels (%lld) != stage-1 rows (%lld)",
               (long long)(p2->C * p2->n_grp), (long long)(p1->D * p1->n_grp));
-  PDD_REQUIRE(pad1_mode == PDD_PAD_ROTATE || (pad1_mode == PDD_PAD_VALUE && pad1vals),
-              "pdd_subband_chain: bad pad mode %d", pad1_mode);
   const int64_t N1 = n_raw / ds;
-  PDD_REQUIRE(N1 > 0 && ld >= n_raw && n_out >= 0 && n_out <= N1 && ld_out >= n_out &&
-                  row_g >= 0 && row_d >= 0,
-              "pdd_subband_chain: bad shape");
+  if (int rc = check_execute({"pdd_subband_chain", N1, 1, ld, n_raw, 0, 0, n_out, N1, ld_out, row_g,
+                              row_d, pad1_mode, pad1vals}))
+    return rc;
   if (n_out == 0) return 0;
   // factorised plans sweep single-group input through their pattern image:
   // they do not chain (pdd.h)
@@ -2182,8 +2164,9 @@ int pdd_subband_chain(const pdd_sweep_plan* p1, const void* x, int64_t n_raw, in
   }
   // stage 1 covers N1 samples in one segment of eighth length Qs1; stage 2
   // reads quarters of length 2 Qs1 (a multiple of its 256-element tile)
-  const int64_t Qs1 = cdiv(cdiv(N1, 8), 64 * p1->v.G) * (64 * p1->v.G);
-  const int64_t ov = std::max(0, p2->max_bin) + 64;
+  // (ov: stage 2's row margin, its delay span + 64 -- its delays are >= 0)
+  const int64_t Qs1 = il_seg(p1, N1).Qs;
+  const int64_t ov = il_seg(p2, n_out).margin;
   if (!(ov <= Qs1 && (2 * Qs1) % (64 * p2->v.G) == 0)) {
     set_error("pdd_subband_chain: block of %lld samples does not chain (stage-2 span %d)",
               (long long)N1, p2->max_bin);
@@ -2210,7 +2193,7 @@ int pdd_subband_chain(const pdd_sweep_plan* p1, const void* x, int64_t n_raw, in
   e1.r2_nR = nR2;
   e1.r2_ov = ov;
   // stage-1 rows (= stage-2 channels): trial d of group g -> row d * n_grp1 + g
-  int rc = execute_il(p1, x, N1, InLayout{ld, 0, 0, 0}, 0, pad1_mode, pad1vals, (float*)R2, 0, N1,
+  int rc = execute_il(p1, x, N1, in_layout(ld), 0, pad1_mode, pad1vals, (float*)R2, 0, N1,
                       1, p1->n_grp, 0.f, stream, e1);
   if (rc == 0) {
     IlExtra e2;
@@ -2218,7 +2201,7 @@ int pdd_subband_chain(const pdd_sweep_plan* p1, const void* x, int64_t n_raw, in
     e2.R_pre = R2;
     e2.Qs_pre = 2 * Qs1;
     e2.nR_pre = nR2;
-    rc = execute_il(p2, nullptr, N1, InLayout{0, 0, 0, 0}, 0, PDD_PAD_VALUE, pad2vals, out, ld_out,
+    rc = execute_il(p2, nullptr, N1, in_layout(0), 0, PDD_PAD_VALUE, pad2vals, out, ld_out,
                     n_out, row_g, row_d, 0.f, stream, e2);
   }
   return rc;

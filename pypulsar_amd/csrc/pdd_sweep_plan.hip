@@ -179,7 +179,7 @@ static bool fx_build(const int32_t* tab, int64_t D, int64_t C, const Variant& v,
       }
   }
   // float32 patterns are built only by the LDS stage 1 from the input rows
-  // (k_fx_patterns_xf: float adds)
+  // (k_fx_stage1<FxFromInput<float>, g>: float adds)
   if (v.S == 4 && T.gtab.empty()) return false;
   // (a quick screen: stage 1 + stage 2 adds against the channel sweep's)
   if (!force && (double)T.n_pat * fx + (double)D * NG > 0.75 * (double)D * C) return false;
@@ -463,7 +463,7 @@ static bool fx_build(const int32_t* tab, int64_t D, int64_t C, const Variant& v,
   // stage 1 per time tile: every pattern's Tq elements (2 KiB of eighths, 4 KiB
   // of quarters), written once for all trial blocks, ~251 CU cycles per 2 KiB
   // pattern row plus ~655 per channel group (its input rows and shift range
-  // staged once): fitted on k_fx_patterns_x, configs[3] g 4 (12.6 ms per
+  // staged once): fitted on k_fx_stage1 (8-bit input), configs[3] g 4 (12.6 ms per
   // 1.04 M-column launch) and the north star g 4 / g 2 (12.65 / 6.48 ms)
   cost_f += ((double)T.n_pat * 251.0 + (double)NG * 655.0) * (double)Tq / 128.0;
   // the channel sweep's interleave pre-pass: every channel's Tq elements per

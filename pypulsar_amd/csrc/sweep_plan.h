@@ -35,10 +35,10 @@ constexpr int il_meta_bytes(int nbuf, int cc, int db) { return il_mr(nbuf) * il_
 #endif
 // window records per chunk: wt[dblk][chunk][kFxWin] (k_sweep_il FX)
 constexpr int kFxWin = 64;
-// Stage 1 through LDS (k_fx_patterns_lds): kFxE-element blocks, groups whose
+// Stage 1 through LDS (k_fx_stage1): kFxE-element blocks, groups whose
 // relative-shift range is <= kFxRspan (checked by the plan: gtab)
 constexpr int kFxE = 512, kFxRspan = 512;
-// float32 stage 1 (k_fx_patterns_xf) builds 1024-element blocks: configs[1]
+// float32 stage 1 (k_fx_stage1<FxFromInput<float>, g>) builds 1024-element blocks: configs[1]
 // f32 7.31 -> 7.10 ms per launch against 512 (8-bit stage 1: 512 best, 12.5
 // against 14.2 ms at 1024)
 constexpr int kFxEf = 1024;

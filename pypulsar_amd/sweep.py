@@ -23,30 +23,50 @@ from . import delays as _delays
 # torch.uint16 where this torch has it
 _U16_TYPES = tuple(t for t in (torch.int16, getattr(torch, "uint16", None)) if t is not None)
 _CODE_OF = {"f32": _lib.F32, "u8": _lib.U8, "u16": _lib.U16}
+# tensor dtype -> plan code: the only input types a sweep takes
+_PLAN_CODE = dict([(torch.float32, _lib.F32), (torch.uint8, _lib.U8)]
+                  + [(t, _lib.U16) for t in _U16_TYPES])
+# _check_input's ``accept``: tensor dtype -> the DMSweep dtype it needs (None: any)
+_ANY_INPUT = dict.fromkeys(_PLAN_CODE)
+_PIECES_INPUT = {torch.uint8: "u8", torch.float32: None}
 
 
-def _is_int_pad(padval):
+def _plan_info(plan):
+    """Plan extents (pdd_sweep_plan_info) as a dict (DMs per block, ...)."""
+    a = np.zeros(8, dtype=np.int64)
+    _lib.check(_lib.lib().pdd_sweep_plan_info(plan, a.ctypes.data_as(ctypes.c_void_p)),
+               "pdd_sweep_plan_info")
+    keys = ("D", "C", "dms_per_block", "samples_per_block", "lds_bytes", "max_bin", "min_bin",
+            "variant")
+    return dict(zip(keys, (int(v) for v in a)))
+
+
+def _plan_timing_read(plan):
+    """(sum of the bracketed sweep-kernel durations in ms, launches) since
+    set_timing / the last read; every launch has its own HIP event pair on
+    the stream it ran on, recorded without host synchronisation."""
+    v = ctypes.c_float(0.0)
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.lib().pdd_sweep_timing_read(plan, ctypes.byref(v), ctypes.byref(n)),
+               "pdd_sweep_timing_read")
+    return float(v.value), int(n.value)
+
+
+def _is_int_pad(padval, vmax=255):
+    """Pads an integer sweep can bake in exactly: integers <= vmax (255 for
+    8-bit, 1023 for 16-bit input) and 'rotate'."""
     if isinstance(padval, str):
         return padval == "rotate"
-    return float(padval).is_integer() and 0 <= float(padval) <= 255
+    return float(padval).is_integer() and 0 <= float(padval) <= vmax
 
 
-def _pads16(x, C, padval):
-    """(pad mode, per-channel pad values) of a 16-bit sweep."""
+def _int_pads(x, C, padval, vmax):
+    """(pad mode, per-channel pad values) of an integer sweep."""
+    if not _is_int_pad(padval, vmax):
+        raise ValueError("integer sweep pads must be integers in [0, %d] or 'rotate'" % vmax)
     if isinstance(padval, str):
-        if padval != "rotate":
-            raise ValueError("16-bit sweep input takes integer or 'rotate' pads")
         return _lib.PAD_ROTATE, None
-    if not (float(padval).is_integer() and 0 <= float(padval) <= 1023):
-        raise ValueError("16-bit sweep pads must be integers in [0, 1023]")
     return _lib.PAD_VALUE, torch.full((C,), float(padval), dtype=torch.float32, device=x.device)
-
-
-def _is_int_pad16(padval):
-    """Pads the 16-bit sweep can bake in exactly (integers <= 1023, 'rotate')."""
-    if isinstance(padval, str):
-        return padval == "rotate"
-    return float(padval).is_integer() and 0 <= float(padval) <= 1023
 
 
 # Test switches applied to every sweep plan this process creates (parity
@@ -111,6 +131,7 @@ class DMSweep(object):
         if self.input_max is not None:
             assert dtype in ("u8", "u16") and 1 <= self.input_max <= (255 if dtype == "u8" else 1023)
         self._plans = {}
+        self._pv0 = {}
 
     def _plan(self, code):
         p = self._plans.get(code)
@@ -121,8 +142,7 @@ class DMSweep(object):
                 tab.ctypes.data_as(ctypes.c_void_p), self.D, self.C, code,
                 self._factor_flags(), ctypes.byref(h)),
                 "pdd_sweep_plan_create_ex")
-            p = h
-            self._plans[code] = p
+            p = self._plans[code] = h
             _apply_test_switches(p)
             if self.input_max is not None and code != _lib.F32:
                 _lib.check(_lib.lib().pdd_sweep_plan_set_input_max(p, self.input_max),
@@ -138,12 +158,39 @@ class DMSweep(object):
                        "pdd_sweep_plan_set_segment_bytes")
 
     def info(self, code=_lib.F32):
-        a = np.zeros(8, dtype=np.int64)
-        _lib.check(_lib.lib().pdd_sweep_plan_info(self._plan(code), a.ctypes.data_as(ctypes.c_void_p)),
-                   "pdd_sweep_plan_info")
-        keys = ("D", "C", "dms_per_block", "samples_per_block", "lds_bytes", "max_bin", "min_bin",
-                "variant")
-        return dict(zip(keys, (int(v) for v in a)))
+        return _plan_info(self._plan(code))
+
+    def _check_input(self, x, accept, out, n_out, N=None, piece=0):
+        """The input check of every execute method; returns ``x``'s plan code.
+        accept: tensor dtype -> the sweep dtype it needs (None: any).  x: [C, N]
+        rows (N None), [C][ld >= N] rows (piece 0) or >= ceil(N / piece)
+        contiguous pieces; out (if any): [D, >= n_out], unit column stride."""
+        if accept.get(x.dtype, "") not in (None, self.dtype):
+            raise TypeError("%s input to a dtype=%r DMSweep; this call takes %s" % (
+                x.dtype, self.dtype, ", ".join("%s (dtype=%r)" % kv for kv in accept.items())))
+        if piece:
+            if not x.is_contiguous() or x.numel() < -(-N // piece) * self.C * piece:
+                raise ValueError("expected >= %d contiguous pieces of [C=%d][%d] samples"
+                                 % (-(-N // piece), self.C, piece))
+        elif x.dim() != 2 or x.shape[0] != self.C or x.stride(1) != 1 or x.shape[1] < (N or 0):
+            raise ValueError("expected a [C=%d, N] device tensor with unit column stride" % self.C)
+        if out is not None and (out.shape[0] != self.D or out.shape[1] < n_out or out.stride(1) != 1):
+            raise ValueError("out must be [D=%d, >= %d] with unit column stride, got %s / %s"
+                             % (self.D, n_out, tuple(out.shape), tuple(out.stride())))
+        return _PLAN_CODE[x.dtype]
+
+    def _zero_pads(self, device, stream):
+        """Per-channel zero pads, allocated once per (device, stream) and
+        filled ON the stream that reads them: a fill on torch's current stream
+        would serialise the CU-partitioned streams of a pipeline, and nothing
+        would order it before the first read."""
+        s = torch.cuda.current_stream(device) if stream is None else stream
+        pv = self._pv0.get((device, s.cuda_stream))
+        if pv is None:
+            with torch.cuda.stream(s):
+                pv = self._pv0[(device, s.cuda_stream)] = torch.zeros(
+                    self.C, dtype=torch.float32, device=device)
+        return pv
 
     def _factor_flags(self):
         f = self.factor
@@ -199,46 +246,31 @@ class DMSweep(object):
             f32 = x.device_data
             raw8 = x._raw8
             x = raw8 if (self.dtype == "u8" and raw8 is not None) else f32
-        if x.dim() != 2 or x.shape[0] != self.C:
-            raise ValueError("expected a [C=%d, N] device tensor" % self.C)
-        if x.stride(1) != 1:
+        if x.dim() == 2 and x.stride(1) != 1:
             x = x.contiguous()
-        N = x.shape[1]
+        N = x.shape[-1]
         if n_out is None:
             n_out = self.n_out(N, trim)
         else:
             n_out = int(n_out)
             if not 0 <= n_out <= N:
                 raise ValueError("n_out=%d outside [0, N=%d]" % (n_out, N))
+        code = self._check_input(x, _ANY_INPUT, out, n_out)
         if out is None:
             out = torch.empty((self.D, n_out), dtype=torch.float32, device=x.device)
-        if out.shape[0] != self.D or out.shape[1] < n_out or out.stride(1) != 1:
-            raise ValueError("out must be [D=%d, >= %d] with unit column stride, got %s / %s"
-                             % (self.D, n_out, tuple(out.shape), tuple(out.stride())))
         if n_out == 0 or N == 0:
             return out
-        if x.dtype == torch.uint8 and not _is_int_pad(padval):
+        if code == _lib.U8 and not _is_int_pad(padval):
             # fractional / statistical pads need the float32 image
             if f32 is None:
                 f32 = torch.empty((self.C, N), dtype=torch.float32, device=x.device)
                 call("pdd_convert_f32", ptr(x), _lib.U8, self.C, N, x.stride(0), ptr(f32), N,
                      stream_ptr(stream))
-            x = f32
-        if x.dtype == torch.uint8:
-            code = _lib.U8
-            if isinstance(padval, str):
-                mode, pv = _lib.PAD_ROTATE, None
-            else:
-                mode = _lib.PAD_VALUE
-                pv = torch.full((self.C,), float(padval), dtype=torch.float32, device=x.device)
-        elif x.dtype in _U16_TYPES:
-            code = _lib.U16
-            mode, pv = _pads16(x, self.C, padval)
-        elif x.dtype == torch.float32:
-            code = _lib.F32
+            x, code = f32, _lib.F32
+        if code == _lib.F32:
             mode, pv = _pad_args(x, padval)
         else:
-            raise TypeError("sweep input must be float32, uint8 or 16-bit")
+            mode, pv = _int_pads(x, self.C, padval, 255 if code == _lib.U8 else 1023)
         if code != _lib.F32 and self.input_max is not None and mode == _lib.PAD_VALUE \
                 and float(padval) > self.input_max:
             # the packed-u16 flush interval assumes every summed value <= input_max
@@ -254,16 +286,12 @@ class DMSweep(object):
         1020, exact) are formed by the interleave pre-pass of the 16-bit sweep
         (pdd_sweep_execute_ds; dtype='u16' plans, ds 2..4).  Pads act on the
         downsampled series (integers <= 1023 or 'rotate')."""
-        if self.dtype != "u16":
-            raise TypeError("sweep_ds needs a dtype='u16' DMSweep")
-        mode, pv = _pads16(x8, self.C, padval)
-        N = x8.shape[1] // int(ds)
+        mode, pv = _int_pads(x8, self.C, padval, 1023)
+        N = x8.shape[-1] // int(ds)
         n_out = self.n_out(N, True) if n_out is None else int(n_out)
+        self._check_input(x8, {torch.uint8: "u16"}, out, n_out)
         if out is None:
             out = torch.empty((self.D, max(n_out, 1)), dtype=torch.float32, device=x8.device)
-        assert x8.dtype == torch.uint8 and x8.dim() == 2 and x8.shape[0] == self.C
-        assert x8.stride(1) == 1 and out.shape[0] == self.D and out.shape[1] >= n_out
-        assert out.stride(1) == 1
         call("pdd_sweep_execute_ds", self._plan(_lib.U16), ptr(x8), x8.shape[1], x8.stride(0),
              int(ds), mode, ptr(pv), ptr(out), out.stride(0), n_out, 0, 1, stream_ptr(stream))
         return out
@@ -275,14 +303,11 @@ class DMSweep(object):
         two), sample s of channel c at xp[(s//piece)*C*piece + c*piece +
         s%piece] (pdd_sweep_execute_ex).  Pads are value 0 (trim=True grids
         with delays >= 0 never read them)."""
-        code = _lib.U8 if xp.dtype == torch.uint8 else _lib.F32
-        if code == _lib.U8 and self.dtype != "u8":
-            raise TypeError("8-bit pieces need a dtype='u8' DMSweep")
-        assert out.shape[0] == self.D and out.shape[1] >= n_out and out.stride(1) == 1
-        assert xp.is_contiguous() and xp.numel() >= -(-N // piece) * self.C * piece
-        pv = torch.zeros(self.C, dtype=torch.float32, device=xp.device)
-        call("pdd_sweep_execute_ex", self._plan(code), ptr(xp), N, 0, piece, x_off, _lib.PAD_VALUE,
-             ptr(pv), ptr(out), out.stride(0), n_out, 0.0, stream_ptr(stream))
+        code = self._check_input(xp, _PIECES_INPUT, out, n_out, N, piece)
+        ld = 0 if piece else xp.stride(0)  # piece 0: channel-major [C][ld] rows
+        call("pdd_sweep_execute_ex", self._plan(code), ptr(xp), N, ld, piece, x_off, _lib.PAD_VALUE,
+             ptr(self._zero_pads(xp.device, stream)), ptr(out), out.stride(0), n_out, 0.0,
+             stream_ptr(stream))
         return out
 
     def pattern_bytes(self, n_out, code=_lib.U8):
@@ -296,20 +321,14 @@ class DMSweep(object):
         into ``out``) or both (3) of sweep_pieces on a factorised plan
         (pdd_sweep_execute_stage): stage 1 of the next block can run on one
         stream while stage 2 of this one runs on another."""
-        code = _lib.U8 if xp.dtype == torch.uint8 else _lib.F32
-        assert out is None or (out.shape[0] == self.D and out.shape[1] >= n_out
-                               and out.stride(1) == 1)
+        code = self._check_input(xp, _PIECES_INPUT, out, n_out, N, piece)
         assert patterns.is_cuda and patterns.is_contiguous()
         nbytes = patterns.numel() * patterns.element_size()
-        # (the zero pads are allocated once: a fill kernel on torch's default
-        # stream would serialise the CU-partitioned streams of a pipeline)
-        pv = getattr(self, "_pv0", None)
-        if pv is None or pv.device != xp.device:
-            pv = self._pv0 = torch.zeros(self.C, dtype=torch.float32, device=xp.device)
         ld = 0 if piece else xp.stride(0)  # piece 0: channel-major [C][ld] rows
         call("pdd_sweep_execute_stage", self._plan(code), ptr(xp), N, ld, piece, x_off,
-             _lib.PAD_VALUE, ptr(pv), ptr(out), out.stride(0) if out is not None else 0, n_out,
-             0.0, ptr(patterns), nbytes, int(stage), stream_ptr(stream))
+             _lib.PAD_VALUE, ptr(self._zero_pads(xp.device, stream)), ptr(out),
+             out.stride(0) if out is not None else 0, n_out, 0.0, ptr(patterns), nbytes, int(stage),
+             stream_ptr(stream))
         return out
 
     def set_timing(self, on=True, code=None):
@@ -325,14 +344,7 @@ class DMSweep(object):
         return self.timing_read()[0]
 
     def timing_read(self):
-        """(sum of the bracketed sweep-kernel durations in ms, launches) since
-        the last read; every launch has its own HIP event pair on the stream
-        it ran on, recorded without host synchronisation."""
-        v = ctypes.c_float()
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().pdd_sweep_timing_read(self._plan(self._timed_code), ctypes.byref(v),
-                                                    ctypes.byref(n)), "pdd_sweep_timing_read")
-        return float(v.value), int(n.value)
+        return _plan_timing_read(self._plan(self._timed_code))
 
     def close(self):
         for p in self._plans.values():
@@ -407,13 +419,7 @@ class GroupedSweep(object):
         return out
 
     def info(self):
-        """Plan extents (pdd_sweep_plan_info) as a dict (DMs per block, ...)."""
-        a = np.zeros(8, dtype=np.int64)
-        _lib.check(_lib.lib().pdd_sweep_plan_info(self._plan, a.ctypes.data_as(ctypes.c_void_p)),
-                   "pdd_sweep_plan_info")
-        keys = ("D", "C", "dms_per_block", "samples_per_block", "lds_bytes", "max_bin", "min_bin",
-                "variant")
-        return dict(zip(keys, (int(v) for v in a)))
+        return _plan_info(self._plan)
 
     def set_timing(self, on=True):
         """Bracket every sweep-kernel launch of this plan with a HIP event pair."""
@@ -421,12 +427,7 @@ class GroupedSweep(object):
                    "pdd_sweep_set_timing")
 
     def timing_read(self):
-        """(summed kernel ms, launches) since set_timing / the last read."""
-        v = ctypes.c_float(0.0)
-        n = ctypes.c_int64(0)
-        _lib.check(_lib.lib().pdd_sweep_timing_read(self._plan, ctypes.byref(v), ctypes.byref(n)),
-                   "pdd_sweep_timing_read")
-        return float(v.value), int(n.value)
+        return _plan_timing_read(self._plan)
 
     def execute_ds(self, x8, ds, n_out, out, row_g, row_d, pad_mode=_lib.PAD_VALUE, padvals=None,
                    stream=None):
@@ -553,7 +554,7 @@ class DDplanExecutor(object):
         results = []
         for s in self.steps:
             # the exact 16-bit path needs the raw 8-bit rows and integer pads
-            use16 = s.u16 and raw8 is not None and _is_int_pad16(padval)
+            use16 = s.u16 and raw8 is not None and _is_int_pad(padval, 1023)
             use8 = (s.two_stage and s.int1 == "u8" and raw8 is not None
                     and _is_int_pad(padval))
             if s.ds > 1 and use16:
@@ -620,9 +621,7 @@ class DDplanExecutor(object):
                 s.sub = torch.empty((s.ncall * s.nsub, s.n_ds), dtype=torch.float32,
                                     device=self.device)
             if use16 or use8:
-                pv = torch.full((x.shape[0],), float(padval), dtype=torch.float32,
-                                device=x.device) if not isinstance(padval, str) else None
-                mode = _lib.PAD_ROTATE if isinstance(padval, str) else _lib.PAD_VALUE
+                mode, pv = _int_pads(x, x.shape[0], padval, 1023 if use16 else 255)
             else:
                 mode, pv = _pad_args(x, padval)
             if use16 and s.ds > 1:

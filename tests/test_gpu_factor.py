@@ -89,6 +89,41 @@ def test_factor_config1_geometry_equals_channel_sweep(gpu):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("pad", [0, "rotate"])
+def test_factor_plain_stage1_without_group_table(gpu, pad):
+    """The plain stage 1 (k_fx_patterns): a forced factorisation whose
+    groups' relative shifts span 722 elements, more than the LDS stage 1
+    holds, so the plan has no group table (pattern_bytes() == 0: no staged
+    execution) and every pattern row is summed from the u16-eighths image.
+    The planner's figures (tests/golden/golden_sweep_plans.json,
+    fx_u8_gtab_empty): 112 patterns, max_bin 5670.  Bit-equal to the
+    channel-by-channel sweep and to the oracle, trimmed and padded."""
+    import torch
+    from pypulsar_amd.sweep import DMSweep
+    C, N, D = 32, 16384, 64
+    freqs = band(C)
+    dms = np.linspace(400, 404, D)
+    x = u8_data(C, N, 47)
+    xd = torch.from_numpy(x).cuda()
+    fx = DMSweep(dms, freqs, DT, dtype="u8", factor="force4")
+    assert fx.factor_info() == (4, 112)
+    assert fx.n_out(N) == N - 5670 == 10714
+    assert fx.pattern_bytes(fx.n_out(N)) == 0
+    plain = DMSweep(dms, freqs, DT, dtype="u8", factor=False)
+    assert plain.factor_info()[0] == 0
+    tab = orc.sweep_table(dms, freqs, DT)
+    for trim in (True, False):
+        a = fx(xd, padval=pad, trim=trim)
+        assert a.shape[1] == (10714 if trim else N)
+        assert torch.equal(a, plain(xd, padval=pad, trim=trim)), (pad, trim)
+        want = orc.sweep_plane(x.astype(np.float64), tab, pad, n_out=a.shape[1])
+        np.testing.assert_array_equal(a.cpu().numpy().astype(np.float64), want,
+                                      err_msg="pad %r trim %s" % (pad, trim))
+    fx.close()
+    plain.close()
+
+
+@pytest.mark.gpu
 def test_factor_segments_and_column_offsets(gpu, monkeypatch):
     """A segment budget that splits the factorised sweep into several
     launches (each with its own interleave + pattern image), and a column
@@ -170,7 +205,7 @@ def test_factor_16bit_input_vs_oracle(gpu, input_max):
 @pytest.mark.parametrize("descending", [True, False])
 @pytest.mark.parametrize("C,g", [(36, 4), (34, 2)])
 def test_factor_f32_small_grids_vs_oracle(gpu, pad, descending, C, g):
-    """Factorised FLOAT32 sweeps (k_fx_patterns_xf + k_sweep_il<..., FX> on the
+    """Factorised FLOAT32 sweeps (k_fx_stage1 from float32 input + k_sweep_il<..., FX> on the
     float32 quarters): forced groups of 4 / 2, value / statistical / rotate
     pads past the block edge, both band orders.  Integer-valued data with an
     integer pad are bit-exact (every partial sum is an integer < 2^24);
@@ -356,3 +391,48 @@ def test_factor_staged_execution_on_cu_partitioned_streams(gpu):
     cu_stream_release(s2)
     sw.close()
     plain.close()
+
+
+@pytest.mark.gpu
+def test_pieces_input_checks_and_side_stream_pads(gpu):
+    """sweep_pieces and sweep_pieces_stage refuse, before any launch (the
+    plane buffer stays untouched): int16 storage (it would be read as
+    float32, past the end of xp), 8-bit pieces on an 'f32' sweep, a short xp
+    and a non-contiguous one.  And a staged call whose FIRST use is on a side
+    stream (the cached zero pads are filled on the stream that reads them)
+    gives the default-stream plane, pads included (n_out = N columns)."""
+    import torch
+    from pypulsar_amd.sweep import DMSweep
+    C, N, D, P = 1024, 1 << 16, 512, 1 << 13
+    freqs = band(C)
+    dms = np.linspace(0, 500, D)
+    x = torch.from_numpy(u8_data(C, N, 70)).cuda()
+    pieces = x.view(C, N // P, P).permute(1, 0, 2)  # [N/P][C][P], not contiguous
+    xp = pieces.contiguous()
+    sw = DMSweep(dms, freqs, DT, dtype="u8", factor="force")
+    f32 = DMSweep(dms, freqs, DT, dtype="f32")
+    n_out = sw.n_out(N)
+    out = torch.full((D, n_out), -1.0, device="cuda")
+    buf = torch.empty(sw.pattern_bytes(N), dtype=torch.uint8, device="cuda")
+    bad = [(sw, xp.to(torch.int16), TypeError), (f32, xp, TypeError),
+           (sw, xp.flatten()[:-1], Exception), (sw, pieces, Exception)]
+    for s, t, err in bad:
+        with pytest.raises(err):
+            s.sweep_pieces(t, N, P, 0, n_out, out)
+        with pytest.raises(err):
+            s.sweep_pieces_stage(t, N, P, 0, n_out, out, buf, 3)
+    torch.cuda.synchronize()
+    assert bool(torch.all(out == -1.0))
+    f32.close()
+    want = torch.empty((D, N), dtype=torch.float32, device="cuda")
+    sw.sweep_pieces_stage(x, N, 0, 0, N, want, buf, 3)
+    side = DMSweep(dms, freqs, DT, dtype="u8", factor="force")
+    got = torch.full((D, N), -1.0, device="cuda")
+    st = torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    side.sweep_pieces_stage(x, N, 0, 0, N, got, buf, 3, stream=st)
+    st.synchronize()
+    assert torch.equal(got, want)
+    assert torch.equal(want, sw(x, padval=0, trim=False))
+    side.close()
+    sw.close()
