@@ -239,6 +239,16 @@ int pdd_sweep_execute_ex(const pdd_sweep_plan* plan, const void* x, int64_t N, i
                          int64_t piece, int64_t x_off, int pad_mode, const float* padvals,
                          float* out, int64_t ld_out, int64_t n_out, float out_bias,
                          void* stream);
+/* The same over TIME-MAJOR input (file order): x is [N][ld_t] spectra, sample
+ * s of channel c at x[s*ld_t + c], ld_t >= the plan's channels; x_off, pads
+ * and out_bias as above.  A factorised plan's stage 1 reads the spectra
+ * directly (8-bit input with x and ld_t multiples of the group size: the
+ * group's channels as one 4- or 2-byte word per spectrum), so a caller that
+ * holds the block in file order needs no pdd_corner_turn before the sweep.
+ * Interleaved tilings only, as for pieces. */
+int pdd_sweep_execute_tm(const pdd_sweep_plan* plan, const void* x, int64_t N, int64_t ld_t,
+                         int64_t x_off, int pad_mode, const float* padvals, float* out,
+                         int64_t ld_out, int64_t n_out, float out_bias, void* stream);
 /* Staged execution of a factorised plan (pdd_sweep_plan_factor > 0, raw-rate
  * input) for pipelining: stage 1 (1: the pattern image, written into
  * `patterns`), stage 2 (2: the sweep, reading the pattern image stage 1 of the

@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "fx_walk.h"
 #include "pdd_internal.h"
 #include "sweep_plan.h"
 
@@ -473,13 +474,16 @@ constexpr int kIlPer = 4;
 // Input layouts of the pre-pass: channel-major rows (x[c * ld + s]) or the
 // "pieces" layout an all-gather of channel-major time slices produces,
 // x[(s / P) * C * P + c * P + s % P] (P = piece, a power of two; C = all
-// channels of the plan).
+// channels of the plan) ...
+// ... or time-major spectra (file order), x[s * ld_t + c].
 struct InLayout {
-  int64_t ld;      // channel-major row stride (piece == 0)
+  int64_t ld;      // channel-major row stride (piece == 0, ld_t == 0)
   int64_t piece;   // P, 0 = channel-major
   int psh;         // log2(P)
   int64_t pstride; // C * P
+  int64_t ld_t;    // time-major spectrum stride, 0 = not time-major
   __device__ __forceinline__ int64_t at(int c, int64_t s) const {
+    if (ld_t) return s * ld_t + c;
     return piece ? (s >> psh) * pstride + (int64_t)c * piece + (s & (piece - 1))
                  : (int64_t)c * ld + s;
   }
@@ -740,6 +744,13 @@ struct FxS1Args : IlArgs {
   const int4* pat;
   const int* gtab;
   int NG;
+  // the persistent form (k_fx_stage1_p): NG x element blocks items, the item
+  // counters of its queues (zeroed before the launch), and whether 8-bit
+  // input may be loaded in aligned words (fx_s1_words)
+  int64_t n_items;
+  unsigned int* queue;
+  int words;
+  int slot;  // byte offset of the item slot in the dynamic LDS (behind the rows)
 };
 
 // Stage-1 sources.  load_row fills one LDS row with the elements [i0, i0 + W)
@@ -758,6 +769,13 @@ struct FxFromImage {
       const int64_t i = i0 + e;
       L[e] = (i >= 0 && i < nR) ? R[(int64_t)c * nR + i] : make_uint4(0u, 0u, 0u, 0u);
     }
+  }
+  // the same element by element (the persistent kernel's prefetch)
+  __device__ __forceinline__ bool inner(int64_t i0, int W, int = 0) const {
+    return i0 >= 0 && i0 + W <= nR;
+  }
+  __device__ __forceinline__ uint4 elem(int c, int64_t i, bool in) const {
+    return (in || (i >= 0 && i < nR)) ? R[(int64_t)c * nR + i] : make_uint4(0u, 0u, 0u, 0u);
   }
 };
 // ... or straight from the input (no image R in HBM): each row element is
@@ -810,34 +828,47 @@ struct FxFromInput {
       L[e] = El::pack(v);
     }
   }
+  // the same element by element (the persistent kernel's prefetch).  inner:
+  // rows [i0, i0 + W) and their samples, widened by `slack` samples, need no test
+  __device__ __forceinline__ bool inner(int64_t i0, int W, int slack = 0) const {
+    const int64_t s_lo = a.base + i0, s_hi = s_lo + W - 1 + (El::S - 1) * a.Qs;
+    return i0 >= 0 && i0 + W <= a.nR && s_lo - slack >= 0 && s_hi + slack < a.N;
+  }
+  __device__ __forceinline__ typename El::elem_t elem(int c, int64_t i, bool in) const {
+    V v[El::S];
+    if (in) {
+#pragma unroll
+      for (int m = 0; m < El::S; ++m) v[m] = (V)src.at(c, a.base + i + m * a.Qs);
+    } else {
+      const V pv = pad_value<V>(a.pad_mode, a.padvals, c);
+#pragma unroll
+      for (int m = 0; m < El::S; ++m)
+        v[m] = (i < 0 || i >= a.nR) ? (V)0
+                                     : padded_sample<V>(src, c, a.base + i + m * a.Qs, a.N, a.pad_mode, pv);
+    }
+    return El::pack(v);
+  }
 };
 
 // Stage 1 through LDS: load the group's FXG rows (Src), then write every
 // pattern of the group from them: pattern element j = the sum of the rows'
 // elements at j + r_k, in channel order ((a + b) + c) + d.
+// The pattern loop: L holds the group's FXG rows, W = kBlock + hi - lo
+// elements each from element j0 + lo on; B0 = the group's first descriptor
+// batch (fx_batch at p0), loaded by the caller.
 template <typename Src, int FXG>
-__global__ __launch_bounds__(256) void k_fx_stage1(const FxS1Args a) {
+__device__ __forceinline__ void fx_write_patterns(const FxS1Args& a, const typename Src::El::elem_t* L,
+                                                  int64_t j0, int p0, int p1, int lo, int W,
+                                                  const FxBatch& B0) {
   using El = typename Src::El;
   using E = typename El::elem_t;
   constexpr int kE = Src::kBlock;
-  extern __shared__ __attribute__((aligned(16))) unsigned char fx_smem[];
-  E* L = reinterpret_cast<E*>(fx_smem);
-  const int* __restrict__ gtab = a.gtab;
   const int4* __restrict__ pat = a.pat;
   E* __restrict__ P = static_cast<E*>(a.R);
   const int64_t nR = a.nR;
-  const int NG = a.NG;
-  const int g = blockIdx.x;
-  const int64_t j0 = (int64_t)blockIdx.y * kE;
-  const int p0 = gtab[g], p1 = gtab[g + 1];
-  const int lo = gtab[NG + 1 + 2 * g], hi = gtab[NG + 2 + 2 * g];
-  const int W = kE + hi - lo;
-  const Src src(a);
-  for (int k = 0; k < FXG; ++k) src.load_row(L + k * W, g * FXG + k, j0 + lo, W);
-  __syncthreads();
-  const int* rng = gtab + 3 * NG + 1;
+  const int* rng = a.gtab + 3 * a.NG + 1;
   for (int pb = p0; pb < p1; pb += 64) {
-    const FxBatch B = fx_batch(pat, rng, pb, p1);
+    const FxBatch B = pb == p0 ? B0 : fx_batch(pat, rng, pb, p1);
     for (int i = 0; i < min(64, p1 - pb); ++i) {
       const int p = pb + i;
       const int4 q = make_int4(0, __builtin_amdgcn_readlane(B.y, i), __builtin_amdgcn_readlane(B.z, i),
@@ -866,18 +897,281 @@ __global__ __launch_bounds__(256) void k_fx_stage1(const FxS1Args a) {
   }
 }
 
+// One workgroup per (group, element block): the rows, a barrier, the
+// patterns.  The form for grids of less than one wave of persistent
+// workgroups (and the persistent kernel's A/B partner, -DPDD_FX_S1_ONESHOT).
+template <typename Src, int FXG>
+__global__ __launch_bounds__(256) void k_fx_stage1(const FxS1Args a) {
+  using E = typename Src::El::elem_t;
+  constexpr int kE = Src::kBlock;
+  extern __shared__ __attribute__((aligned(16))) unsigned char fx_smem[];
+  E* L = reinterpret_cast<E*>(fx_smem);
+  const int* __restrict__ gtab = a.gtab;
+  const int NG = a.NG;
+  const int g = blockIdx.x;
+  const int64_t j0 = (int64_t)blockIdx.y * kE;
+  const int p0 = gtab[g], p1 = gtab[g + 1];
+  const int lo = gtab[NG + 1 + 2 * g], hi = gtab[NG + 2 + 2 * g];
+  const int W = kE + hi - lo;
+  const Src src(a);
+  for (int k = 0; k < FXG; ++k) src.load_row(L + k * W, g * FXG + k, j0 + lo, W);
+  __syncthreads();
+  if (p1 > p0)
+    fx_write_patterns<Src, FXG>(a, L, j0, p0, p1, lo, W,
+                                fx_batch(a.pat, gtab + 3 * NG + 1, p0, p1));
+}
+
+// The persistent form: a grid of (resident workgroups per CU) x (CUs)
+// workgroups takes (group, element block) ITEMS in the order of fx_walk.h
+// (group fastest) from one queue per XCD -- queue x holds items x, x + 8, ...;
+// a workgroup drains the queue of its own XCD first, then the others' -- and
+// holds item i + 1's rows in registers (issued before item i's pattern loop,
+// written to LDS after the barrier that ends it), so the input loads run
+// under the pattern stores.  What a thread holds for the next item:
+// FxPreElems, packed elements (FXG x ceil(W / 256) <= 3 or 5; float32 and image
+// elements are the loaded words themselves) ...
+template <typename Src, int FXG>
+struct FxPreElems {
+  using E = typename Src::El::elem_t;
+  // (rows wider than kWmax elements -- relative shifts spanning more than 256
+  // -- are not prefetched: they load at commit, the way the one-item kernel does)
+  static constexpr int kWmax = Src::kBlock + 256;
+  static constexpr int kPer = (kWmax + 255) / 256;
+  E r[FXG][kPer];
+  __device__ __forceinline__ void fetch(const Src& src, int c0, int64_t i0, int W) {
+    if (W > kWmax) return;
+    const bool in = src.inner(i0, W);
+#pragma unroll
+    for (int k = 0; k < FXG; ++k)
+#pragma unroll
+      for (int n = 0; n < kPer; ++n) {
+        const int e = threadIdx.x + n * 256;
+        if (e < W) r[k][n] = src.elem(c0 + k, i0 + e, in);
+      }
+  }
+  __device__ __forceinline__ void commit(const Src& src, E* L, int c0, int64_t i0, int W) const {
+    if (W > kWmax) {
+      for (int k = 0; k < FXG; ++k) src.load_row(L + k * W, c0 + k, i0, W);
+      return;
+    }
+#pragma unroll
+    for (int k = 0; k < FXG; ++k)
+#pragma unroll
+      for (int n = 0; n < kPer; ++n) {
+        const int e = threadIdx.x + n * 256;
+        if (e < W) L[k * W + e] = r[k][n];
+      }
+  }
+};
+// ... or, for 8-bit input on interior blocks of aligned input (FxS1Args.words),
+// raw words, unpacked into the u16 eighths only on the way to LDS: mode 1 (rows:
+// channel-major or pieces) = the 4 consecutive samples of one row, one dword
+// per eighth, so a thread's unit is 4 consecutive elements of a row (the
+// window is widened to dword boundaries: up to 3 samples read on either
+// side, hence the slack of `inner`, are dropped); mode 2 (time-major) = the
+// group's FXG channels of one spectrum, one FXG-byte word per eighth, so a
+// unit is one element of all FXG rows.  Mode 0: edge blocks and unaligned
+// input load their rows at commit the way the one-item kernel does.
+template <int FXG>
+struct FxPreWords {
+  using Src = FxFromInput<uint8_t>;
+  // (rows wider than kWmax elements -- relative shifts spanning more than 256
+  // -- are not prefetched: 4 units per thread cover FXG x (kWmax / 4 + 1))
+  static constexpr int kWmax = kFxE + 256;
+  static constexpr int kUnits = FXG * ((kWmax + 3) / 4 + 1) > kWmax ? FXG * ((kWmax + 3) / 4 + 1) : kWmax;
+  static constexpr int kU = (kUnits + 255) / 256;
+  uint32_t d[kU][8];
+  int mode, sh, nq;
+  __device__ __forceinline__ void fetch(const Src& src, int c0, int64_t i0, int W) {
+    const FxS1Args& a = src.a;
+    const uint8_t* __restrict__ x = src.src.x;
+    const int64_t s0 = a.base + i0;
+    mode = 0;
+    if (!a.words || W > kWmax) return;
+    if (a.lay.ld_t) {
+      if (!src.inner(i0, W)) return;
+      mode = 2;
+#pragma unroll
+      for (int n = 0; n < kU; ++n) {
+        const int e = threadIdx.x + n * 256;
+        if (e < W) {
+#pragma unroll
+          for (int m = 0; m < 8; ++m) {
+            const uint8_t* q = x + (s0 + e + m * a.Qs) * a.lay.ld_t + c0;
+            if constexpr (FXG == 4) d[n][m] = *reinterpret_cast<const uint32_t*>(q);
+            else d[n][m] = *reinterpret_cast<const uint16_t*>(q);
+          }
+        }
+        // (one unit's 8 addresses at a time: scheduling all units' loads
+        // together spills registers at 4 waves per SIMD)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      return;
+    }
+    if (!src.inner(i0, W, 3)) return;
+    mode = 1;
+    sh = (int)(s0 & 3);
+    nq = (W + sh + 3) >> 2;
+    if (a.lay.piece) fetch_rows<true>(a, x, c0, s0 - sh);
+    else fetch_rows<false>(a, x, c0, s0 - sh);
+  }
+  template <bool PIECES>
+  __device__ __forceinline__ void fetch_rows(const FxS1Args& a, const uint8_t* __restrict__ x, int c0,
+                                             int64_t sa) {
+#pragma unroll
+    for (int n = 0; n < kU; ++n) {
+      const int f = threadIdx.x + n * 256;
+      if (f < FXG * nq) {
+        const int k = f / nq, q = f - k * nq;
+        const int64_t s = sa + 4 * q;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+          const int64_t sm = s + m * a.Qs;
+          const int64_t o = PIECES ? (sm >> a.lay.psh) * a.lay.pstride + (int64_t)(c0 + k) * a.lay.piece +
+                                         (sm & (a.lay.piece - 1))
+                                   : (int64_t)(c0 + k) * a.lay.ld + sm;
+          d[n][m] = *reinterpret_cast<const uint32_t*>(x + o);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  __device__ __forceinline__ void commit(const Src& src, uint4* L, int c0, int64_t i0, int W) const {
+    if (mode == 0) {
+      for (int k = 0; k < FXG; ++k) src.load_row(L + k * W, c0 + k, i0, W);
+      return;
+    }
+    if (mode == 2) {
+#pragma unroll
+      for (int n = 0; n < kU; ++n) {
+        const int e = threadIdx.x + n * 256;
+        if (e < W) {
+#pragma unroll
+          for (int k = 0; k < FXG; ++k) {
+            uint32_t v[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) v[m] = (d[n][m] >> (8 * k)) & 0xffu;
+            L[k * W + e] = ElemU16::pack(v);
+          }
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int n = 0; n < kU; ++n) {
+      const int f = threadIdx.x + n * 256;
+      if (f < FXG * nq) {
+        const int k = f / nq, q = f - k * nq;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int e = 4 * q - sh + j;
+          uint32_t v[8];
+#pragma unroll
+          for (int m = 0; m < 8; ++m) v[m] = (d[n][m] >> (8 * j)) & 0xffu;
+          if (e >= 0 && e < W) L[k * W + e] = ElemU16::pack(v);
+        }
+      }
+    }
+  }
+};
+
+// An item's geometry from the group table.
+struct FxItem {
+  int g, p0, p1, lo, W;
+  int64_t j0;
+};
+template <int kE>
+__device__ __forceinline__ FxItem fx_item(const FxS1Args& a, int i) {
+  const FxWalkItem w = fx_walk_item(i, a.NG);
+  const int* __restrict__ gtab = a.gtab;
+  const int g = w.group;
+  const int lo = gtab[a.NG + 1 + 2 * g], hi = gtab[a.NG + 2 + 2 * g];
+  return {g, gtab[g], gtab[g + 1], lo, kE + hi - lo, w.block * kE};
+}
+// The next item of queue `xcd` from its ticket (the queue counter's value
+// before this workgroup's increment), or of the next queue that has one; -1:
+// none left.  (Counters stay far below 2^32: n_items < 2^31 - 16 x grid.)
+__device__ __forceinline__ int fx_take(unsigned int* queue, int xcd, unsigned int ticket, int n_items) {
+  for (int t = 0;; ++t) {
+    const int64_t i = (int64_t)ticket * kFxXcds + xcd;
+    if (i < n_items) return (int)i;
+    if (t == kFxXcds - 1) return -1;
+    xcd = (xcd + 1) % kFxXcds;
+    ticket = atomicAdd(queue + xcd, 1u);
+  }
+}
+
+// (The u16-eighths instances keep the register budget of 4 waves per SIMD --
+// 4 workgroups per CU, what their LDS allows at rspan <= 128; the float32
+// rows of 1024 elements leave room for 2.)
+template <typename Src, int FXG>
+__global__ __launch_bounds__(256, Src::kBlock == kFxE ? 4 : 2) void k_fx_stage1_p(const FxS1Args a) {
+  using E = typename Src::El::elem_t;
+  using Pre = typename std::conditional<std::is_same<Src, FxFromInput<uint8_t>>::value, FxPreWords<FXG>,
+                                        FxPreElems<Src, FXG>>::type;
+  constexpr int kE = Src::kBlock;
+  extern __shared__ __attribute__((aligned(16))) unsigned char fx_smem[];
+  E* L = reinterpret_cast<E*>(fx_smem);
+  // (item numbers pass from thread 0 to the workgroup through two words
+  // behind the rows)
+  int* slot = reinterpret_cast<int*>(fx_smem + a.slot);
+  const int n_items = (int)a.n_items;
+  const int xcd = fx_walk_xcd(blockIdx.x);
+  if (threadIdx.x == 0) {
+    slot[0] = fx_take(a.queue, xcd, atomicAdd(a.queue + xcd, 1u), n_items);
+    slot[1] = fx_take(a.queue, xcd, atomicAdd(a.queue + xcd, 1u), n_items);
+  }
+  __syncthreads();
+  const int first = __builtin_amdgcn_readfirstlane(slot[0]);
+  int nx = __builtin_amdgcn_readfirstlane(slot[1]);
+  if (first < 0) return;
+  const Src src(a);
+  Pre pre;
+  // (the descriptor loads of an item's first 64 patterns travel with its
+  // rows: a load issued inside the pattern loop would wait for the prefetch)
+  const int* rng = a.gtab + 3 * a.NG + 1;
+  FxItem cur = fx_item<kE>(a, first);
+  FxBatch Bc = {0, 0, 0, 0, 0};
+  if (cur.p1 > cur.p0) Bc = fx_batch(a.pat, rng, cur.p0, cur.p1);
+  pre.fetch(src, cur.g * FXG, cur.j0 + cur.lo, cur.W);
+  pre.commit(src, L, cur.g * FXG, cur.j0 + cur.lo, cur.W);
+  for (;;) {
+    __syncthreads();  // item cur's rows are in LDS; every thread has read the slot
+    FxItem nxt = cur;
+    FxBatch Bn = Bc;
+    if (nx >= 0) {
+      nxt = fx_item<kE>(a, nx);
+      if (nxt.p1 > nxt.p0) Bn = fx_batch(a.pat, rng, nxt.p0, nxt.p1);
+      pre.fetch(src, nxt.g * FXG, nxt.j0 + nxt.lo, nxt.W);
+    }
+    fx_write_patterns<Src, FXG>(a, L, cur.j0, cur.p0, cur.p1, cur.lo, cur.W, Bc);
+    if (nx < 0) break;
+    // the item after next.  (Taken here, not before the pattern loop: the
+    // compiler waits for an atomic's result where it is issued, and with it
+    // for the prefetch loads in flight.)
+    if (threadIdx.x == 0) slot[0] = fx_take(a.queue, xcd, atomicAdd(a.queue + xcd, 1u), n_items);
+    __syncthreads();  // every thread has read item cur's rows
+    const int nn = __builtin_amdgcn_readfirstlane(slot[0]);
+    pre.commit(src, L, nxt.g * FXG, nxt.j0 + nxt.lo, nxt.W);
+    cur = nxt;
+    Bc = Bn;
+    nx = nn;
+  }
+}
+
 // Every LDS stage-1 instance (groups of 2 or 4: fx_build makes no others):
-// (source, group size) -> kernel.  src: the plan's dtype when stage 1 reads
+// (source, group size) -> kernels.  src: the plan's dtype when stage 1 reads
 // the input, kFxImage when it reads a pre-pass image.
 typedef void (*fx_s1_fn)(FxS1Args);
 constexpr int kFxImage = -1;
 struct FxS1Instance {
   int src, fx;
-  fx_s1_fn fn;
-  int block;  // elements per workgroup (the source's kBlock)
+  fx_s1_fn fn, fn_p;  // one item per workgroup / persistent
+  int block;          // elements per item (the source's kBlock)
 };
-#define PDD_FX_S1(SRC_, ...) \
-  {SRC_, 2, k_fx_stage1<__VA_ARGS__, 2>, __VA_ARGS__::kBlock}, {SRC_, 4, k_fx_stage1<__VA_ARGS__, 4>, __VA_ARGS__::kBlock}
+#define PDD_FX_S1(SRC_, ...)                                                              \
+  {SRC_, 2, k_fx_stage1<__VA_ARGS__, 2>, k_fx_stage1_p<__VA_ARGS__, 2>, __VA_ARGS__::kBlock}, \
+  {SRC_, 4, k_fx_stage1<__VA_ARGS__, 4>, k_fx_stage1_p<__VA_ARGS__, 4>, __VA_ARGS__::kBlock}
 static const FxS1Instance kFxS1Instances[] = {
     PDD_FX_S1(kFxImage, FxFromImage), PDD_FX_S1(PDD_U8, FxFromInput<uint8_t>),
     PDD_FX_S1(PDD_U16, FxFromInput<uint16_t>), PDD_FX_S1(PDD_F32, FxFromInput<float>)};
@@ -1617,6 +1911,9 @@ struct pdd_sweep_plan : pdd::PlanDims {
   int* d_sig = nullptr;    // factorised, delay-aligned tiles: [Dpad] per-trial skew (fx_skew)
   int input_max = 0;       // largest input value (integer input; 0 = the dtype's bound)
   int poison = 0;          // pdd_sweep_plan_set_poison: 0xFF-fill the pattern image (tests)
+  // factorised, LDS stage 1: workgroups of the persistent grid (resident per
+  // CU x CUs of the plan's device) with the pre-pass image / the input as source
+  int fx_s1_wgs[2] = {0, 0};
   int64_t seg_bytes = 0;   // pdd_sweep_plan_set_segment_bytes: segment budget cap (0 = default)
   // timing of the sweep kernel (pdd_sweep_set_timing): one event pair per
   // bracketed launch, recorded on the execute stream without host syncs
@@ -1774,6 +2071,21 @@ static int il_build_image(const IlRun& r, const IlSeg& g, int64_t t_base) {
   return -3;
 }
 
+// Dynamic LDS of an LDS stage-1 instance: the group's rows (the persistent
+// kernel adds kFxSlotBytes for its item slot).
+constexpr size_t kFxSlotBytes = 16;
+static size_t fx_s1_lds(const pdd_sweep_plan* p, const FxS1Instance& k) {
+  return (size_t)(p->fx * (k.block + p->fx_rspan)) * sizeof(uint4);
+}
+// 8-bit input the persistent stage 1 may load in aligned words (FxPreWords):
+// time-major, the fx channels of a group as one fx-byte word per spectrum;
+// rows and pieces, 4 consecutive samples of a row as one dword.
+static bool fx_s1_words(const void* x, const InLayout& lay, int fx, int64_t Qs) {
+  const uintptr_t xa = (uintptr_t)x;
+  if (lay.ld_t) return xa % fx == 0 && lay.ld_t % fx == 0;
+  return xa % 4 == 0 && Qs % 4 == 0 && (lay.piece ? lay.piece % 4 == 0 : lay.ld % 4 == 0);
+}
+
 // Part 2 (factorised plans): the segment's pattern image by stage 1.
 static int il_build_patterns(const IlRun& r, const IlSeg& g, int64_t t_base) {
   const pdd_sweep_plan* p = r.p;
@@ -1795,11 +2107,27 @@ static int il_build_patterns(const IlRun& r, const IlSeg& g, int64_t t_base) {
   for (const FxS1Instance& k : kFxS1Instances) {
     if (k.src != (r.fx_direct ? p->dtype : kFxImage) || k.fx != p->fx) continue;
     const int NG = (int)(p->C / p->fx);
-    const FxS1Args a{{r.fx_direct ? r.x : r.R, r.lay, r.N, t_base + g.lo + r.x_off, g.Qs, g.nR,
-                      r.pad_mode, r.padvals, r.P},
-                     (const int4*)p->d_pat, p->d_gtab, NG};
-    hipLaunchKernelGGL(k.fn, dim3((unsigned)NG, (unsigned)cdiv(g.nR, k.block)), dim3(256),
-                       (size_t)(p->fx * (k.block + p->fx_rspan)) * sizeof(uint4), r.st, a);
+    FxS1Args a{{r.fx_direct ? r.x : r.R, r.lay, r.N, t_base + g.lo + r.x_off, g.Qs, g.nR,
+                r.pad_mode, r.padvals, r.P},
+               (const int4*)p->d_pat, p->d_gtab, NG, 0, nullptr, 0, 0};
+    const int64_t nblk = cdiv(g.nR, k.block);
+    const size_t lds = fx_s1_lds(p, k);
+    const int wgs = p->fx_s1_wgs[r.fx_direct];
+    a.n_items = NG * nblk;
+#ifndef PDD_FX_S1_ONESHOT
+    // more than one wave of persistent workgroups: the persistent kernel
+    if (wgs > 0 && a.n_items > wgs && a.n_items < (1ll << 31) - 16ll * wgs) {
+      a.queue = static_cast<unsigned int*>(scratch(r.st, kScratchSmall, kFxXcds * sizeof(unsigned int)));
+      if (!a.queue) return -2;
+      if (hipMemsetAsync(a.queue, 0, kFxXcds * sizeof(unsigned int), r.st) != hipSuccess)
+        return il_launch_failed();
+      a.words = r.fx_direct && p->dtype == PDD_U8 && fx_s1_words(r.x, r.lay, p->fx, g.Qs);
+      a.slot = (int)lds;
+      hipLaunchKernelGGL(k.fn_p, dim3((unsigned)wgs), dim3(256), lds + kFxSlotBytes, r.st, a);
+      return hipGetLastError() == hipSuccess ? 0 : il_launch_failed();
+    }
+#endif
+    hipLaunchKernelGGL(k.fn, dim3((unsigned)NG, (unsigned)nblk), dim3(256), lds, r.st, a);
     return hipGetLastError() == hipSuccess ? 0 : il_launch_failed();
   }
   set_error("pdd_sweep_execute: no stage-1 kernel (groups of %d, dtype %d)", p->fx, p->dtype);
@@ -1934,10 +2262,24 @@ static int plan_create(const int32_t* host_table, int64_t n_grp, int64_t D, int6
   if (e == hipSuccess && !sp.fxt.gtab.empty()) {
     e = upload(&p->d_gtab, sp.fxt.gtab);
     // the LDS stage 1 (gtab: every group's shift range fits kFxRspan)
-    for (const FxS1Instance& k : kFxS1Instances)
+    int dev = 0, cus = 0;
+    if (e == hipSuccess) e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    for (const FxS1Instance& k : kFxS1Instances) {
+      const int lds_max = (int)(4 * (kFxEf + kFxRspan) * sizeof(uint4));
       if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(4 * (kFxEf + kFxRspan) * sizeof(uint4)));
+        e = hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k.fn_p, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                lds_max + (int)kFxSlotBytes);
+      // the persistent grid of this plan's instances: what the device holds at once
+      if (e == hipSuccess && k.fx == p->fx && (k.src == kFxImage || k.src == p->dtype)) {
+        int per_cu = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k.fn_p, 256,
+                                                         fx_s1_lds(p, k) + kFxSlotBytes);
+        p->fx_s1_wgs[k.src != kFxImage] = per_cu * cus;
+      }
+    }
   }
   if (e != hipSuccess) {
     set_error("pdd_sweep_plan_create: %s", hipGetErrorString(e));
@@ -1979,7 +2321,7 @@ static int check_execute(const ExecShape& a) {
 }
 // Channel-major rows ld apart, or pieces of `piece` samples of C channels.
 static InLayout in_layout(int64_t ld, int64_t piece = 0, int64_t C = 0) {
-  InLayout lay{ld, piece, 0, C * piece};
+  InLayout lay{ld, piece, 0, C * piece, 0};
   while ((1ll << lay.psh) < piece) ++lay.psh;
   return lay;
 }
@@ -2061,6 +2403,23 @@ int pdd_sweep_execute_ex(const pdd_sweep_plan* p, const void* x, int64_t N, int6
                      p->stride, (int)n_tblk, (int)p->n_dblk);
   PDD_LAUNCHED();
   return 0;
+}
+
+int pdd_sweep_execute_tm(const pdd_sweep_plan* p, const void* x, int64_t N, int64_t ld_t,
+                         int64_t x_off, int pad_mode, const float* padvals, float* out,
+                         int64_t ld_out, int64_t n_out, float out_bias, void* stream) {
+  PDD_REQUIRE(p && x && out, "pdd_sweep_execute_tm: null pointer");
+  // (the spectrum stride takes the row stride's place in the checks: >= all channels)
+  if (int rc = check_execute({"pdd_sweep_execute_tm", N, 1, ld_t, p->C * p->n_grp, 0, x_off, n_out,
+                              kAnyColumns, ld_out, 0, 0, pad_mode, padvals}))
+    return rc;
+  if (n_out == 0) return 0;
+  PDD_REQUIRE(p->v.kind == 0, "pdd_sweep_execute_tm: the generic (sparse-grid) kernel reads "
+              "channel-major input");
+  InLayout lay = in_layout(0);
+  lay.ld_t = ld_t;
+  return execute_il(p, x, N, lay, x_off, pad_mode, padvals, out, ld_out, n_out, 0, 1, out_bias,
+                    stream);
 }
 
 int64_t pdd_sweep_pattern_bytes(const pdd_sweep_plan* p, int64_t n_out) {

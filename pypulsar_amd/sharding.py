@@ -113,6 +113,12 @@ def _corner_turn(src_tc, dst_cm):
          dst_cm.stride(0), stream_ptr())
 
 
+# One rank, factorised plan whose stage 1 reads the input itself: sweep each
+# batch straight from the time-major ``part`` (DMSweep.sweep_timemajor) -- no
+# per-batch corner turn, no channel-major copy of the block.
+TIME_MAJOR_STAGE1 = True
+
+
 class DMShardedSweep(object):
     """Pipelined DM-sharded sweep of ONE filterbank block across the ranks
     (north star; BASELINE configs[3]).
@@ -145,6 +151,12 @@ class DMShardedSweep(object):
     input up to col_edges[k+1] + max_bin <= (k+1)T.  All delays are >= 0
     (cur_dm = 0, dms >= 0, reference = the highest frequency), so no pad is
     ever read.
+
+    One rank (world 1, not a rehearsal, nothing injected) with a factorised
+    plan whose stage 1 reads the input itself (``tm``): nothing is exchanged
+    or turned -- ``exchange_batch`` remembers ``part`` and ``sweep_batch(k)``
+    sweeps batch k's columns from ``part.view(N, C)`` in file order
+    (pdd_sweep_execute_tm); the channel-major block ``x`` is not allocated.
 
     Plans (delay table, sweep plan, buffers) are built once in __init__;
     ``work`` (per-trial weights, e.g. ``trial_work``) balances the DM slices.
@@ -213,9 +225,21 @@ class DMShardedSweep(object):
         self.rows = self.hi - self.lo
         self.gather = bool(gather)
         self.dst = dst
+        self.sw = None
+        if sweep_fn is None and self.rows:
+            from .sweep import DMSweep
+            self.sw = DMSweep(self.dms[self.lo:self.hi], self.freqs, dt,
+                              dtype="u8" if dtype == torch.uint8 else "f32", factor=factor)
+        self.tm = bool(TIME_MAJOR_STAGE1 and self.world == 1 and not self.rehearse
+                       and self.sw is not None and to_cm is None and gather_fn is None
+                       and x_buf is None
+                       and self.sw.direct_stage1(_codes()[dtype]))
+        self._part = None
         # buffers (reused every call)
         xshape = (self.N // self.P, self.C, self.P) if self.pieces else (self.C, self.N)
-        if x_buf is not None:
+        if self.tm:
+            self.x = None
+        elif x_buf is not None:
             assert tuple(x_buf.shape) == xshape and x_buf.dtype == dtype and x_buf.is_contiguous()
             self.x = x_buf
         else:
@@ -226,7 +250,7 @@ class DMShardedSweep(object):
         if self.pieces:
             # two corner-turn buffers: batch k+1's turn must not overwrite the
             # one batch k's all-gather may still be reading
-            self.cm = ([] if self.direct else
+            self.cm = ([] if self.direct or self.tm else
                        [torch.empty((self.C, self.P), dtype=dtype, device=self.device)
                         for _ in range(2)])
             self.xt = None
@@ -244,14 +268,7 @@ class DMShardedSweep(object):
             self.planes = [torch.empty((self.rows, c), dtype=torch.float32, device=self.device)
                            for c in cols]
         self.to_cm = to_cm if to_cm is not None else _corner_turn
-        self.sw = None
         if sweep_fn is None:
-            from .sweep import DMSweep
-            code = "u8" if dtype == torch.uint8 else "f32"
-            if self.rows:
-                self.sw = DMSweep(self.dms[self.lo:self.hi], self.freqs, dt, dtype=code,
-                                  factor=factor)
-
             def sweep_fn(x, N, piece, x_off, dms_slice, out, n_cols):
                 if piece:
                     self.sw.sweep_pieces(x, N, piece, x_off, n_cols, out)
@@ -284,6 +301,9 @@ class DMShardedSweep(object):
         """Batch k into x: this rank's corner turn (+ the async all-gather of
         every rank's slice); returns the pending collective or None."""
         W, T, P = self.world, self.T, self.P
+        if self.tm:
+            self._part = part
+            return None
         if self.direct:
             # this rank's own slice only; the others' are already in x
             r = self.rank
@@ -316,6 +336,11 @@ class DMShardedSweep(object):
         if not self.pieces and W > 1 and not self.rehearse:
             self.to_cm(self.xt[k * T:(k + 1) * T], self.x[:, k * T:(k + 1) * T])
         a, b = self.col_edges[k], self.col_edges[k + 1]
+        if self.tm:
+            if b > a:
+                self.sw.sweep_timemajor(self._part.reshape(self.N, self.C), self.N, a, b - a,
+                                        self.planes[k])
+            return []
         if self.rows and b > a:
             self.sweep_fn(self.x, self.N, self.P if self.pieces else 0, a,
                           self.dms[self.lo:self.hi], self.planes[k], b - a)
@@ -361,7 +386,7 @@ class DMShardedSweep(object):
             self.sw.close()
             self.sw = None
         self.sweep_fn = None
-        self.x = self.full = self.planes = None
+        self.x = self.full = self.planes = self._part = None
 
 
 def timeshard_edges(n_out, world, align=1024):

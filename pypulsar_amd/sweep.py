@@ -310,6 +310,31 @@ class DMSweep(object):
              stream_ptr(stream))
         return out
 
+    def sweep_timemajor(self, x_tc, N, x_off, n_out, out, stream=None):
+        """Plane columns [x_off, x_off + n_out) of the sweep of a block held
+        TIME-MAJOR (file order): ``x_tc`` = [>= N, C] spectra with unit channel
+        stride, sample s of channel c at x_tc[s, c] (pdd_sweep_execute_tm).
+        A factorised plan's stage 1 reads the spectra directly, so no corner
+        turn precedes the sweep.  Pads are value 0 (trim=True grids with
+        delays >= 0 never read them)."""
+        if x_tc.dim() != 2 or x_tc.shape[1] != self.C or x_tc.stride(1) != 1 or x_tc.shape[0] < N:
+            raise ValueError("expected a [>= %d, C=%d] device tensor with unit channel stride"
+                             % (N, self.C))
+        if x_tc.dtype not in _PLAN_CODE:
+            raise TypeError("%s input: a sweep takes float32, uint8 or 16-bit samples" % x_tc.dtype)
+        if out.shape[0] != self.D or out.shape[1] < n_out or out.stride(1) != 1:
+            raise ValueError("out must be [D=%d, >= %d] with unit column stride" % (self.D, n_out))
+        call("pdd_sweep_execute_tm", self._plan(_PLAN_CODE[x_tc.dtype]), ptr(x_tc), N,
+             x_tc.stride(0), x_off, _lib.PAD_VALUE, ptr(self._zero_pads(x_tc.device, stream)),
+             ptr(out), out.stride(0), n_out, 0.0, stream_ptr(stream))
+        return out
+
+    def direct_stage1(self, code=_lib.U8):
+        """True when the plan for ``code`` is factorised with the stage 1 that
+        reads the input itself (any layout, no pre-pass image):
+        pdd_sweep_pattern_bytes is non-zero for exactly those plans."""
+        return self.pattern_bytes(1, code) > 0
+
     def pattern_bytes(self, n_out, code=_lib.U8):
         """Bytes of the pattern image one staged launch of ``n_out`` columns
         needs (0: not a factorised plan; pdd_sweep_pattern_bytes)."""
