@@ -448,6 +448,26 @@ int pdd_acc_search(const float* powers, int64_t D, int nz, int64_t ni, const int
                    int n_harms, const float* thr, int64_t rlo, int32_t* cands, int64_t max_cands,
                    unsigned long long* count, void* stream);
 
+/* ---- Fourier-domain interference zapping (pypulsar_amd/zap.py; restated in
+ * tests/zap_oracle.py).  powers: whitened powers of pdd_ps_normalise, one
+ * spectrum a row. */
+/* out[k] = the rank-th smallest (1-based, 1 <= rank <= R) of powers[r ld + k],
+ * r < R, for every k < nn: exact selection, the value returned is one of the
+ * column's, whatever the ties (-0 counts as below +0).  1 <= R <= 64.  The
+ * inputs are finite by construction (pdd_ps_normalise writes 0 for a dead
+ * row): a NaN is outside the contract (the result of such a column is
+ * unspecified, nothing else is affected). */
+int pdd_zap_percentile(const float* powers, int64_t R, int64_t nn, int64_t ld, int rank,
+                       float* out, void* stream);
+/* bins: DEVICE int32 [nz][2], inclusive bin intervals [lo, hi], sorted,
+ * disjoint, 1 <= lo <= hi < nn.  In each of the D rows powers[d ldp + k] = 1
+ * for lo <= k <= hi -- the whitened mean level -- and, where spec is not
+ * null (interleaved (re, im) float32, row stride lds in COMPLEX elements),
+ * spec[d lds + k] = (0.70710677, 0.70710677), of unit power.  Nothing else is
+ * written.  nz == 0 or D == 0: nothing is launched. */
+int pdd_zap_apply(float* powers, int64_t ldp, float* spec, int64_t lds, int64_t D, int64_t nn,
+                  const int32_t* bins, int64_t nz, void* stream);
+
 /* ---- folding of plane rows at candidate periods and the search of the folds
  * over period / period-derivative offsets (pypulsar_amd/fold.py; restated in
  * tests/fold_oracle.py).  Phase is a 64-bit unsigned fraction of a turn with

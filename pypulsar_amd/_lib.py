@@ -54,7 +54,7 @@ EXPORTS = (
     "pdd_ps_harmsum", "pdd_ps_search", "pdd_fold_rows", "pdd_fold_search",
     "pdd_acc_correlate", "pdd_acc_search", "pdd_rfi_stats_prep", "pdd_rfi_stats_power",
     "pdd_rfi_apply", "pdd_ffa_plan_info", "pdd_ffa_downsample", "pdd_ffa_detrend", "pdd_ffa_pass",
-    "pdd_ffa_search", "pdd_sweep_execute_tm",
+    "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
 )
 
 
@@ -153,6 +153,8 @@ _SIGS = {
     "pdd_ffa_pass": ([_vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _vp, _int,
                       ctypes.c_double, _vp, _vp, _i64, _vp, _vp], _int),
     "pdd_ffa_search": ([_vp, _vp, _i64, _i64, _i64, ctypes.c_float, _vp, _i64, _vp, _vp], _int),
+    "pdd_zap_percentile": ([_vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
+    "pdd_zap_apply": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp], _int),
 }
 
 

@@ -210,18 +210,27 @@ class AccelSearch(object):
         volume (4 nz) -- within the periodicity search's WORKSPACE_BYTES."""
         return max(1, _per.WORKSPACE_BYTES // ((24 + 4 * self.nz) * int(nfft)))
 
-    def __call__(self, plane, dms, dt, row_batch=None, nfft=None):
+    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None):
+        """``zap``: a ``pypulsar_amd.zap.Zaplist`` whose bins of the whitened
+        spectrum are set to the whitened mean level in every row before the
+        correlation (None: nothing is zapped)."""
         dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
         D, n = plane.shape
         assert len(dms) == D, "one DM per plane row"
         nfft = self.ps.default_nfft(n) if nfft is None else int(nfft)
         step = self.row_batch(nfft) if row_batch is None else int(row_batch)
         assert step >= 1
+        if zap is not None:
+            from . import zap as _zap
+            zbins = _zap.device_bins(zap.bins(nfft, dt, nfft // 2), nfft // 2, plane.device)
         parts = []
         for r0 in range(0, D, step):
             spec = self.ps.spectrum(plane[r0:r0 + step], nfft)
-            _, white = self.ps.normalise(spec, want_spectrum=True)
+            wpow, white = self.ps.normalise(spec, want_spectrum=True)
             del spec
+            if zap is not None:
+                _zap.apply(wpow, zbins, white)
+            del wpow
             powers = self.correlate(white, n)
             c, k = self.raw(powers, nfft, dt)
             parts.append(self.collect(c, k, dms, n, nfft, dt, row0=r0))

@@ -21,13 +21,19 @@ their ``z``, and a fold starts from their frequency derivative.  With
 ``--ffa`` the plane is also searched by fast folding (pypulsar_amd.ffa: slow,
 narrow pulses that the harmonic sums lose); its sifted candidates go to
 ``<base>.ffacands`` in the same layout, and ``--fold K`` folds its K strongest
-as ``<base>_ffacand<k>``.
+as ``<base>_ffacand<k>``.  With ``--zaplist FILE`` and / or ``--autozap`` the
+Fourier bins of periodic interference -- listed in a PRESTO ``.zaplist``, or
+found on the plane as the bins that stand out in (nearly) every DM row
+(pypulsar_amd.zap) -- are set to the whitened mean level before the
+periodicity or acceleration search.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --autozap obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zaplist site.zaplist obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --ffa --ffa-pmin 0.5 --ffa-pmax 10 \\
         --fold 3 obs.fil
 """
@@ -42,7 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
                 nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2, maskfile=None,
-                rfifind=None):
+                rfifind=None, zaplist=None, autozap=None):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
     pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
@@ -50,7 +56,12 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     ACCEL_CAND_DTYPE) on a z grid of ``dz``; ``harms`` then at most 16.
     ``maskfile`` / ``rfifind``: the cells of that rfifind ``.mask``, or of the
     one made here from the data with intervals of ``rfifind`` seconds (left as
-    <base>_rfifind.mask), are replaced by their channel's level first."""
+    <base>_rfifind.mask), are replaced by their channel's level first.
+    ``zaplist`` (a ``.zaplist`` file name or a ``pypulsar_amd.zap.Zaplist``) /
+    ``autozap`` (a ``pypulsar_amd.zap.BirdieFinder``, or True for the default
+    one, run on the swept plane; its list is left as <base>.zaplist): the
+    Fourier bins of those intervals are set to the whitened mean level in
+    every DM row before the search; both: the two lists merged."""
     import torch
     from pypulsar_amd.formats import filterbank
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
@@ -89,7 +100,24 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
         ps = AccelSearch(sigma, zmax, dz, harms or ACCEL_HARMS, flo=flo)
     else:
         ps = PeriodicitySearch(sigma, harms or DEFAULT_HARMS, flo=flo)
-    cands = ps(plane, dms, dt, row_batch=row_batch, nfft=nfft)
+    kw = {}
+    if zaplist is not None or autozap is not None:
+        from pypulsar_amd import zap as _zap
+        zl = _zap.Zaplist()
+        if zaplist is not None:
+            zl = zaplist if isinstance(zaplist, _zap.Zaplist) else _zap.read_zaplist(zaplist)
+        if autozap is not None:
+            finder = autozap if isinstance(autozap, _zap.BirdieFinder) else _zap.BirdieFinder()
+            nf = PeriodicitySearch.default_nfft(plane.shape[1]) if nfft is None else int(nfft)
+            found = finder.find(ps.ps if zmax > 0 else ps, plane, dt, nfft=nf)
+            out = os.path.splitext(infile)[0] + ".zaplist"
+            _zap.write_zaplist(out, found)
+            b = found.bins(nf, dt)
+            print("autozap: %d intervals, %d of %d bins zapped -> %s" % (
+                len(b), int(np.sum(b[:, 1] - b[:, 0] + 1)), nf // 2, out))
+            zl = zl.merged(found)
+        kw["zap"] = zl
+    cands = ps(plane, dms, dt, row_batch=row_batch, nfft=nfft, **kw)
     sw.close()
     if return_plane:
         return cands, dt, plane
@@ -113,6 +141,23 @@ def main(argv=None):
     parser.add_option("--rfifind", type="float", default=None, metavar="SECONDS",
                       help="Make the mask from the data first, with intervals of SECONDS "
                            "(written to <INFILE base>_rfifind.mask), then search with it.")
+    parser.add_option("--zaplist", type="string", default=None, metavar="FILE",
+                      help="PRESTO .zaplist of periodic interference: its Fourier bins are set "
+                           "to the whitened mean level in every DM row before the periodicity "
+                           "or acceleration search.  (The fast-folding search works in the "
+                           "time domain and is not affected.)")
+    parser.add_option("--autozap", action="store_true", default=False,
+                      help="Find the periodic interference on the swept plane first (bins "
+                           "whose percentile across DM rows stands out), write it to <INFILE "
+                           "base>.zaplist and search with it; with --zaplist the two lists "
+                           "are merged.  (Not applied to the fast-folding search.)")
+    parser.add_option("--autozap-rows", dest="autozap_rows", type="int", default=33,
+                      help="DM rows, evenly spaced, that --autozap uses (at most 64). "
+                           "(Default: 33)")
+    parser.add_option("--autozap-percent", dest="autozap_percent", type="float", default=50.0,
+                      help="Percentile across those rows. (Default: 50, the median)")
+    parser.add_option("--autozap-nsig", dest="autozap_nsig", type="float", default=5.0,
+                      help="Per-bin false-alarm level of --autozap in sigma. (Default: 5)")
     parser.add_option("-s", "--sigma", type="float", default=6.0,
                       help="Single-trial candidate threshold in sigma. (Default: 6)")
     parser.add_option("--numharm", type="int", default=16,
@@ -169,11 +214,19 @@ def main(argv=None):
     numharm = min(options.numharm, 16) if options.zmax > 0 else options.numharm
     harms = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= numharm) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
+    finder = None
+    if options.autozap:
+        from pypulsar_amd.zap import MAX_ROWS, BirdieFinder
+        if not 1 <= options.autozap_rows <= MAX_ROWS:
+            parser.error("--autozap-rows must be in 1..%d" % MAX_ROWS)
+        finder = BirdieFinder(options.autozap_rows, options.autozap_percent,
+                              options.autozap_nsig)
     res = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
                       options.flo, options.nfft, options.row_batch,
                       return_plane=options.fold > 0 or options.ffa, zmax=options.zmax,
                       dz=options.dz,
-                      maskfile=options.maskfile, rfifind=options.rfifind)
+                      maskfile=options.maskfile, rfifind=options.rfifind,
+                      zaplist=options.zaplist, autozap=finder)
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]

@@ -291,19 +291,27 @@ class PeriodicitySearch(object):
         FFT's own work area) within WORKSPACE_BYTES."""
         return max(1, WORKSPACE_BYTES // (20 * int(nfft)))
 
-    def __call__(self, plane, dms, dt, row_batch=None, nfft=None):
+    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None):
+        """``zap``: a ``pypulsar_amd.zap.Zaplist`` whose bins are set to the
+        whitened mean level in every row before the search (None: nothing is
+        zapped)."""
         dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
         D, n = plane.shape
         assert len(dms) == D, "one DM per plane row"
         nfft = self.default_nfft(n) if nfft is None else int(nfft)
         step = self.row_batch(nfft) if row_batch is None else int(row_batch)
         assert step >= 1
+        if zap is not None:
+            from . import zap as _zap
+            zbins = _zap.device_bins(zap.bins(nfft, dt, nfft // 2), nfft // 2, plane.device)
         parts = []
         for r0 in range(0, D, step):
             rows = plane[r0:r0 + step]
             spec = self.spectrum(rows, nfft)
             powers = self.normalise(spec)
             del spec
+            if zap is not None:
+                _zap.apply(powers, zbins)
             c, k = self.raw(powers, nfft, dt)
             parts.append(self.collect(c, k, dms, nfft, dt, row0=r0))
             del powers, c, k
