@@ -371,6 +371,33 @@ int pdd_sp_search(const float* x, int64_t D, int64_t n, int64_t ld, int64_t L, c
                   const int32_t* widths, int n_widths, float threshold, int32_t* cands,
                   int64_t max_cands, unsigned long long* count, void* stream);
 
+/* ---- grouping of single-pulse candidates across DM row, time and width
+ * (pypulsar_amd/spgroup.py; restated by brute force in
+ * tests/spgroup_oracle.py).  A candidate is the record {row, start, width,
+ * float-bits snr} of pdd_sp_search; its extent is [start, start + width).
+ * Candidates a, b are linked when |row_a - row_b| <= row_tol and
+ * max(start_a, start_b) - min(end_a, end_b) <= time_tol (negative: the
+ * extents overlap); a group is a connected component of the links.
+ * 0 <= row_tol <= 16, 0 <= time_tol <= 1023, 1 <= width <= 1025, start >= 0,
+ * start + width + time_tol < 2^31, k < 2^31.  Canonical order: ascending by
+ * (start / 1024, row, start, width, snr bits as int32). */
+/* cands: DEVICE int32 [k][4], 16-byte aligned, in canonical order (the
+ * kernels need the order of the cell key (start / 1024) * nrows + row only);
+ * nrows > every row.  label[i] = the index of the first member of i's
+ * group: the same for any scheduling.  Memory: the k labels, nothing
+ * proportional to the plane.  k == 0: nothing is launched. */
+int pdd_spg_label(const int32_t* cands, int64_t k, int64_t nrows, int row_tol, int time_tol,
+                  int32_t* label, void* stream);
+/* groups: DEVICE int32 [k][8], 16-byte aligned, written whole by the call:
+ * at index g == label[g]: {members, best, row_lo, row_hi, start_lo, end_hi,
+ * snr bits of best, 0} -- best: the index of the member of the highest S/N
+ * compared as floats, the smallest index on a tie (a NaN is outside the
+ * contract); start_lo = min start, end_hi = max (start + width); at every
+ * other index: zeros.  Integer atomics only: the same bits for any
+ * scheduling. */
+int pdd_spg_summarise(const int32_t* cands, const int32_t* label, int64_t k, int32_t* groups,
+                      void* stream);
+
 /* ---- periodicity search of a DM-time plane (pypulsar_amd/periodicity.py;
  * the arithmetic of PrestoFFT.deredden, formats/prestofft.py:151-195, and
  * PrestoFFT.harmonic_sum, :98-113).  Spectra are interleaved (re, im)

@@ -55,6 +55,7 @@ EXPORTS = (
     "pdd_acc_correlate", "pdd_acc_search", "pdd_rfi_stats_prep", "pdd_rfi_stats_power",
     "pdd_rfi_apply", "pdd_ffa_plan_info", "pdd_ffa_downsample", "pdd_ffa_detrend", "pdd_ffa_pass",
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
+    "pdd_spg_label", "pdd_spg_summarise",
 )
 
 
@@ -155,6 +156,8 @@ _SIGS = {
     "pdd_ffa_search": ([_vp, _vp, _i64, _i64, _i64, ctypes.c_float, _vp, _i64, _vp, _vp], _int),
     "pdd_zap_percentile": ([_vp, _i64, _i64, _i64, _int, _vp, _vp], _int),
     "pdd_zap_apply": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp], _int),
+    "pdd_spg_label": ([_vp, _i64, _i64, _int, _int, _vp, _vp], _int),
+    "pdd_spg_summarise": ([_vp, _vp, _i64, _vp, _vp], _int),
 }
 
 

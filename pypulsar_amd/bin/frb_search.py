@@ -15,10 +15,16 @@ file's DM-time plane.  Output: PRESTO-style ``.singlepulse`` text.
         --downsamp 2 --threshold 7 -o obs.singlepulse obs.fil
     python -m pypulsar_amd.bin.frb_search --rfifind 2.0 --numdms 2048 obs.fil
     python -m pypulsar_amd.bin.frb_search --mask obs_rfifind.mask --numdms 2048 obs.fil
+    python -m pypulsar_amd.bin.frb_search --group --min-members 3 --min-group-dm 5 obs.fil
 
 ``--mask`` / ``--rfifind``: the cells of an rfifind ``.mask`` (read, or made in
 a first pass over the file: pypulsar_amd.rfi) are replaced on the device by
 their channel's level before the zero-DM filter.
+
+``--group``: after the stream ends the merged candidates are grouped across
+DM row, time and width on the device (pypulsar_amd.spgroup: one line per
+event, not per DM trial) and the kept groups written to ``<out base>.spgroups``;
+the ``.singlepulse`` file is the same with or without it.
 """
 import optparse
 import os
@@ -118,6 +124,18 @@ def main(argv=None):
                       help="Largest boxcar width in downsampled samples (<= 1025).")
     parser.add_option("-o", "--outname", default=None,
                       help="Output .singlepulse file (default: INFILE with .singlepulse).")
+    parser.add_option("--group", action="store_true", default=False,
+                      help="Group the candidates across DM, time and width; the kept groups "
+                           "go to <out base>.spgroups.")
+    parser.add_option("--group-rows", type="int", default=2, metavar="N",
+                      help="Candidates up to N DM trials apart can be linked. (Default: 2)")
+    parser.add_option("--group-samples", type="int", default=3, metavar="N",
+                      help="Candidates whose extents are up to N downsampled samples apart "
+                           "can be linked. (Default: 3)")
+    parser.add_option("--min-members", type="int", default=1, metavar="N",
+                      help="Keep groups of at least N candidates. (Default: 1)")
+    parser.add_option("--min-group-dm", type="float", default=None, metavar="DM",
+                      help="Drop groups whose best member is below DM. (Default: keep all)")
     parser.add_option("-d", "--debug", action="store_true", default=False)
     options, args = parser.parse_args(argv)
     if len(args) != 1:
@@ -131,6 +149,15 @@ def main(argv=None):
     out = options.outname or os.path.splitext(args[0])[0] + ".singlepulse"
     write_singlepulse(cands, out)
     print("%d candidates -> %s" % (len(cands), out))
+    if options.group:
+        from pypulsar_amd.spgroup import SinglePulseGrouper, select, write_groups
+        # (the merged list is grouped once; its rows are those of the DM grid)
+        _, groups = SinglePulseGrouper(options.group_rows, options.group_samples)(cands, dms=dms)
+        kept = select(groups, options.min_members, options.min_group_dm)
+        gout = os.path.splitext(out)[0] + ".spgroups"
+        write_groups(kept, gout)
+        print("%d candidates -> %d groups -> %d kept -> %s"
+              % (len(cands), len(groups), len(kept), gout))
     return 0
 
 
