@@ -11,7 +11,9 @@ pypulsar_amd/csrc/pdd_accel.hip implement:
 * ``interpolate_reference``  PrestoFFT.interpolate (formats/prestofft.py:76-96)
       verbatim -- with its ``np.sinc(pi * d)`` -- and with the sinc corrected;
 * ``grid`` / ``taps``  the z grid, the half-widths and the normalised taps;
-* ``plane``  ``P[j][i] = |sum_e F[k0 + e] t[j][phi][e]|^2``;
+* ``plane``  ``P[j][i] = |sum_e F[k0 + e] t[j][phi][e]|^2``; ``plane_f32``
+      the same sums the plain way in float32; ``impulse_plane``  the plane of
+      a row of unit impulses, from given taps;
 * ``stage_sum`` / ``candidates``  the harmonic stages on the top harmonic's
       grid (float32, ascending h) and the candidate rule.
 
@@ -104,6 +106,51 @@ def plane(F, t, M):
             assert len(A) == nn
             P[j, phi::2] = np.abs(A) ** 2
     return P
+
+
+def plane_f32(F, t, M):
+    """``plane`` evaluated the plain way in float32: the taps rounded to
+    float32, the sum over e sequential from e = -M, every product and every
+    addition rounded (no fused multiply-add).  F: complex64 [nn]; t as from
+    ``taps`` (any subset of its z); returns P float32 [nz][2 nn]."""
+    F = np.asarray(F).astype(np.complex64)
+    nn = len(F)
+    z = np.zeros(M, dtype=np.float32)
+    fr = np.concatenate((z, F.real.astype(np.float32), z))
+    fi = np.concatenate((z, F.imag.astype(np.float32), z))
+    tr, ti = t.real.astype(np.float32), t.imag.astype(np.float32)
+    P = np.empty((t.shape[0], 2 * nn), dtype=np.float32)
+    for j in range(t.shape[0]):
+        for phi in (0, 1):
+            re = np.zeros(nn, dtype=np.float32)
+            im = np.zeros(nn, dtype=np.float32)
+            for e in np.flatnonzero((tr[j, phi] != 0) | (ti[j, phi] != 0)):
+                a, b = fr[e:e + nn], fi[e:e + nn]
+                re = (re + a * tr[j, phi, e]) - b * ti[j, phi, e]
+                im = (im + a * ti[j, phi, e]) + b * tr[j, phi, e]
+            P[j, phi::2] = re * re + im * im
+            assert re.dtype == np.float32
+    return P
+
+
+def impulse_plane(t, hw, M, nn, bins):
+    """The plane of a row that is 1 + 0i at ``bins`` and 0 elsewhere, from
+    taps given as (re, im) pairs [nz][2][2 M + 1][2] (of any float type; the
+    arithmetic is float64): A[j][2 k0 + phi] = sum over the bins k with
+    |k - k0| <= hw_j of t[j][phi][M + (k - k0)].  Returns (P float64 [nz][2
+    nn], support bool [nz][2 nn]: the positions within hw_j of a bin)."""
+    t = np.asarray(t, dtype=np.float64)
+    t = t[..., 0] + 1j * t[..., 1]
+    nz = t.shape[0]
+    A = np.zeros((nz, 2 * nn), dtype=np.complex128)
+    support = np.zeros((nz, 2 * nn), dtype=bool)
+    for j in range(nz):
+        for k in bins:
+            k0 = np.arange(max(0, k - int(hw[j])), min(nn, k + int(hw[j]) + 1))
+            for phi in (0, 1):
+                A[j, 2 * k0 + phi] += t[j, phi, M + (k - k0)]
+                support[j, 2 * k0 + phi] = True
+    return A.real * A.real + A.imag * A.imag, support
 
 
 def stage_sum(P, H):

@@ -202,3 +202,113 @@ def test_stage_sum_floors_negative_z():
     S = ao.stage_sum(Q, 4)
     i = np.arange(ni)
     np.testing.assert_array_equal(S[2], ((i + 2) // 4 + (2 * i + 2) // 4 + (3 * i + 2) // 4 + i))
+
+
+# ---- the banks, grids and records of the edge cases (tests/test_gpu_accel_edges.py) ----
+
+@pytest.mark.parametrize("n,nfft,zmax,dz,nz,M", [(90, 200, 10, 3, 7, 46), (600, 1024, 7, 1, 15, 34),
+                                                 (1144, 4096, 254, 2, 255, 512)])
+def test_product_bank_other_dz_and_limits(n, nfft, zmax, dz, nz, M):
+    from pypulsar_amd import accel
+    t, hw, Mo = ao.taps(n, nfft, zmax, dz)
+    taps, hw2, M2 = accel.template_bank(n, nfft, zmax, dz)
+    assert Mo == M2 == M and len(hw) == nz and np.array_equal(hw2, hw)
+    assert taps.dtype == np.float32 and taps.shape == (nz, 2, 2 * M + 1, 2)
+    ref = np.stack((t.real, t.imag), axis=-1)
+    err = np.max(np.abs(taps - ref))
+    print("bank (%d, %d, %d, %d): max |taps - oracle| = %.3g" % (n, nfft, zmax, dz, err))
+    assert err <= 2.0 ** -24  # rounded once (|t| <= 1)
+    zs, J0 = accel.z_grid(zmax, dz)
+    assert J0 == zmax // dz and np.array_equal(zs, ao.grid(zmax, dz)[0])
+
+
+def test_bank_and_grid_limits():
+    from pypulsar_amd import accel
+    # (127 + 16) / (1143 / 4096) = 512.45: a half-width of 513
+    assert ao.taps(1143, 4096, 254)[2] == 513
+    with pytest.raises(ValueError):
+        accel.template_bank(1143, 4096, 254)
+    with pytest.raises(ValueError):
+        accel.z_grid(256, 2)  # 257 z values
+    assert len(accel.z_grid(254, 2)[0]) == 255
+    zs, J0 = accel.z_grid(10, 3)
+    assert J0 == 3 and np.array_equal(zs, [-9.0, -6.0, -3.0, 0.0, 3.0, 6.0, 9.0])
+
+
+@pytest.mark.parametrize("dz", [1, 3])
+def test_to_records_other_dz(dz):
+    from pypulsar_amd import accel
+    n, nfft, dt = 3000, 4096, 1e-3
+    bits = int(np.float32(30.0).view(np.int32))
+    # (row, i, jc, H, bits, 0)
+    c = np.asarray([[0, 700, 0, 1, bits, 0], [0, 2102, -2, 3, bits, 0], [1, 2101, 0, 3, bits, 0],
+                    [1, 2804, 7, 4, bits, 0], [0, 1401, -8, 2, bits, 0], [1, 1050, -1, 3, bits, 0]],
+                   dtype=np.int32)
+    recs = accel.to_records(c, [10.0, 20.0], n, nfft, dt, dz)
+    want = sorted((int(d), int(H), i / (2.0 * H), jc * dz / float(H)) for d, i, jc, H, _, _ in c)
+    assert [(int(r["row"]), int(r["numharm"]), float(r["r"]), float(r["z"])) for r in recs] == want
+    zero = recs["z"] == 0
+    assert zero.sum() == 2 and not np.any(np.signbit(recs["z"][zero]))  # jc = 0: 0.0, not -0.0
+    assert not np.any(np.signbit(recs["zbins"][zero])) and not np.any(np.signbit(recs["fd"][zero]))
+    assert np.array_equal(recs["DM"], 10.0 * (recs["row"] + 1))
+    T = n * dt
+    np.testing.assert_allclose(recs["zbins"], recs["z"] * nfft / n, rtol=1e-15)
+    np.testing.assert_allclose(recs["fd"], recs["z"] / (T * T), rtol=1e-15)
+    np.testing.assert_allclose(recs["freq"], recs["r"] / (nfft * dt), rtol=1e-15)
+    np.testing.assert_allclose(recs["accel"], recs["fd"] * accel.C_LIGHT / recs["freq"], rtol=1e-15)
+    assert np.array_equal(np.sign(recs["accel"]), np.sign(recs["z"]))
+
+
+@pytest.mark.parametrize("H", [5, 7, 16])
+def test_stage_sum_against_the_definition(H):
+    """S[j][i] = the float32 sum in ascending h of P[J0 + floor((jc h + H // 2)
+    / H)][floor((i h + H // 2) / H)], cell by cell with exact fractions."""
+    from fractions import Fraction
+    from math import floor
+    nz, ni, J0 = 3, 41, 1
+    P = np.random.default_rng(H).exponential(1.0, (nz, ni)).astype(np.float32)
+    S = ao.stage_sum(P, H)
+    assert S.dtype == np.float32 and S.shape == (nz, ni)
+    for j in range(nz):
+        for i in range(ni):
+            s = None
+            for h in range(1, H + 1):
+                v = P[J0 + floor(Fraction((j - J0) * h + H // 2, H)), floor(Fraction(i * h + H // 2, H))]
+                s = v if s is None else np.float32(s + v)
+            assert s.dtype == np.float32 and S[j, i] == s
+    # the floors, for one negative row by hand: jc = -1, H = 7 (H // 2 = 3):
+    # floor((3 - h) / 7) = 0 for h <= 3 and -1 beyond
+    if H == 7:
+        Q = (100.0 * np.arange(nz)[:, None] + np.zeros(ni)).astype(np.float32)
+        assert ao.stage_sum(Q, 7)[0, 0] == 3 * 100.0 + 4 * 0.0
+
+
+def test_float32_correlation_is_within_the_gpu_bar():
+    """A plain sequential float32 evaluation of the sums of the largest bank
+    (M = 512, nn = 2048) against the float64 plane: the bar of the GPU tests,
+    max |P - P_ref| / max P_ref <= 2e-5, leaves a correct kernel about
+    tenfold margin."""
+    n, nfft = 1144, 4096
+    t, hw, M = ao.taps(n, nfft, 254)
+    assert M == 512 and (hw[0], hw[127], hw[254]) == (512, 58, 512)
+    t = t[[0, 127, 254]]
+    rng = np.random.default_rng(5)
+    F = ((rng.normal(size=2048) + 1j * rng.normal(size=2048)) / np.sqrt(2.0)).astype(np.complex64)
+    ref = ao.plane(F, t, M)
+    got = ao.plane_f32(F, t, M)
+    assert got.dtype == np.float32
+    err = np.max(np.abs(got.astype(np.float64) - ref)) / np.max(ref)
+    print("float32 sequential, M = 512: max |P - P_ref| / max P_ref = %.3g" % err)
+    assert err <= 2e-5
+
+
+def test_impulse_plane_is_the_plane_of_an_impulse():
+    n, nfft = 90, 200
+    t, hw, M = ao.taps(n, nfft, 10, 3)
+    F = np.zeros(100, dtype=np.complex128)
+    F[[0, 99]] = 1.0
+    pairs = np.stack((t.real, t.imag), axis=-1)
+    P, support = ao.impulse_plane(pairs, hw, M, 100, (0, 99))
+    np.testing.assert_allclose(P, ao.plane(F, t, M), rtol=1e-12, atol=1e-300)
+    assert np.all(P[~support] == 0) and np.all(P[support] > 0)
+    assert support[3].sum() == 2 * 2 * (hw[3] + 1) and hw[3] == 36
