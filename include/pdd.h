@@ -398,6 +398,43 @@ int pdd_spg_label(const int32_t* cands, int64_t k, int64_t nrows, int row_tol, i
 int pdd_spg_summarise(const int32_t* cands, const int32_t* label, int64_t k, int32_t* groups,
                       void* stream);
 
+/* ---- cut-outs of single-pulse candidates: the dedispersed frequency-time
+ * image and the DM-time image of many candidates from one block of the file
+ * (pypulsar_amd/cutout.py; restated by brute force in
+ * tests/cutout_oracle.py).
+ * x: DEVICE time-major block [n][C], row stride ld elements, PDD_U8 or
+ * PDD_F32 (the file's order: no corner turn).  table: DEVICE int32
+ * [rows][C] delay bins (delays.sweep_table).  padvals: DEVICE float32 [C],
+ * or NULL for 0: what a sample outside rows 0..n-1 of the block contributes.
+ * jobs: DEVICE int64 [J][5] = {t0, f, row0, bmin, bmax}: t0 the first raw
+ * row of the image relative to the block's first row (negative allowed,
+ * |t0| <= 2^40), f the samples summed per bin (1 <= f <= fmax), row0 the
+ * job's first table row; bmin <= every entry of the job's ndm table rows
+ * <= bmax (read by pdd_cutout_dmt only).
+ * Limits: 1 <= nbin, ndm <= 1024, 1 <= fmax <= 1024, C fmax 255 < 2^31,
+ * nsub divides C; anything else is refused (-1).  A job that breaks what is
+ * stated about it (f, row0, bmin/bmax, span) touches no memory outside the
+ * buffers: its image is NaN.
+ * 8-bit input: float32(exact integer sum of the in-range samples) + the
+ * float32 pad term; float32 input: float32 sums in a fixed order.  No
+ * atomics: the same bits however the jobs are batched. */
+/* out: DEVICE float32 [J][nsub][nbin],
+ *   out[j][s][b] = sum_{c in subband s} sum_{k<f} X(c, t0 + b f + k + table[row0][c]),
+ * subband s = channels s C/nsub .. (s+1) C/nsub - 1. */
+int pdd_cutout_ft(const void* x, int dtype, int64_t n, int64_t C, int64_t ld, const int64_t* jobs,
+                  int64_t J, const int32_t* table, int64_t rows, const float* padvals, int nbin,
+                  int nsub, int fmax, float* out, void* stream);
+/* out: DEVICE float32 [J][ndm][nbin],
+ *   out[j][d][b] = sum_{all c} sum_{k<f} X(c, t0 + b f + k + table[row0 + d][c]).
+ * span >= (nbin + ceil((bmax - bmin + 1) / f)) f of every job, <= 2^22: the
+ * positions of a job's per-channel box sums.  work: DEVICE scratch of
+ * work_bytes >= span C e bytes (e = 2 for PDD_U8 with fmax <= 257, else 4),
+ * 4-byte aligned; as many jobs as fit it go through each pair of launches. */
+int pdd_cutout_dmt(const void* x, int dtype, int64_t n, int64_t C, int64_t ld, const int64_t* jobs,
+                   int64_t J, const int32_t* table, int64_t rows, const float* padvals, int nbin,
+                   int ndm, int fmax, int64_t span, void* work, int64_t work_bytes, float* out,
+                   void* stream);
+
 /* ---- periodicity search of a DM-time plane (pypulsar_amd/periodicity.py;
  * the arithmetic of PrestoFFT.deredden, formats/prestofft.py:151-195, and
  * PrestoFFT.harmonic_sum, :98-113).  Spectra are interleaved (re, im)

@@ -55,7 +55,7 @@ EXPORTS = (
     "pdd_acc_correlate", "pdd_acc_search", "pdd_rfi_stats_prep", "pdd_rfi_stats_power",
     "pdd_rfi_apply", "pdd_ffa_plan_info", "pdd_ffa_downsample", "pdd_ffa_detrend", "pdd_ffa_pass",
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
-    "pdd_spg_label", "pdd_spg_summarise",
+    "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
 )
 
 
@@ -158,6 +158,10 @@ _SIGS = {
     "pdd_zap_apply": ([_vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp], _int),
     "pdd_spg_label": ([_vp, _i64, _i64, _int, _int, _vp, _vp], _int),
     "pdd_spg_summarise": ([_vp, _vp, _i64, _vp, _vp], _int),
+    "pdd_cutout_ft": ([_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _int, _int, _int,
+                       _vp, _vp], _int),
+    "pdd_cutout_dmt": ([_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _int, _int, _int,
+                        _i64, _vp, _i64, _vp, _vp], _int),
 }
 
 

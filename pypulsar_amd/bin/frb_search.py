@@ -16,6 +16,7 @@ file's DM-time plane.  Output: PRESTO-style ``.singlepulse`` text.
     python -m pypulsar_amd.bin.frb_search --rfifind 2.0 --numdms 2048 obs.fil
     python -m pypulsar_amd.bin.frb_search --mask obs_rfifind.mask --numdms 2048 obs.fil
     python -m pypulsar_amd.bin.frb_search --group --min-members 3 --min-group-dm 5 obs.fil
+    python -m pypulsar_amd.bin.frb_search --cutouts 20 --min-members 3 obs.fil
 
 ``--mask`` / ``--rfifind``: the cells of an rfifind ``.mask`` (read, or made in
 a first pass over the file: pypulsar_amd.rfi) are replaced on the device by
@@ -25,6 +26,12 @@ their channel's level before the zero-DM filter.
 DM row, time and width on the device (pypulsar_amd.spgroup: one line per
 event, not per DM trial) and the kept groups written to ``<out base>.spgroups``;
 the ``.singlepulse`` file is the same with or without it.
+
+``--cutouts N`` (implies ``--group``): the frequency-time and DM-time images
+(pypulsar_amd.cutout) of the best member of the N strongest kept groups, from
+the raw file (masked when a mask is in use; the zero-DM filter is not
+applied), go to ``<out base>_cutouts.npz``; the ``.singlepulse`` and
+``.spgroups`` files are the same with or without it.
 """
 import optparse
 import os
@@ -73,7 +80,9 @@ def get_mask(infile, fb, maskfile=None, rfifind=None, block=1 << 18):
 
 
 def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=6.0,
-                widths=None, detrendlen=1024, debug=False, maskfile=None, rfifind=None):
+                widths=None, detrendlen=1024, debug=False, maskfile=None, rfifind=None,
+                rfimask=None):
+    """``rfimask``: a mask already made (else ``maskfile`` / ``rfifind``)."""
     import torch
     from pypulsar_amd.formats import filterbank
     from pypulsar_amd.search import DEFAULT_WIDTHS, StreamingSearch, merge
@@ -85,7 +94,8 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
     ss = StreamingSearch(dms, fb.freqs, fb.tsamp, block=block, downsamp=downsamp,
                          zero_dm=zero_dm, dtype=tdt, threshold=threshold,
                          widths=widths or DEFAULT_WIDTHS, detrendlen=detrendlen,
-                         rfimask=get_mask(infile, fb, maskfile, rfifind, block))
+                         rfimask=rfimask if rfimask is not None else
+                         get_mask(infile, fb, maskfile, rfifind, block))
     parts = []  # candidate times are relative to the file start
     for i, c in enumerate(ss(_chunks(fb, block))):
         parts.append(c)
@@ -136,6 +146,20 @@ def main(argv=None):
                       help="Keep groups of at least N candidates. (Default: 1)")
     parser.add_option("--min-group-dm", type="float", default=None, metavar="DM",
                       help="Drop groups whose best member is below DM. (Default: keep all)")
+    parser.add_option("--cutouts", type="int", default=0, metavar="N",
+                      help="Cut out the frequency-time and DM-time images of the best member "
+                           "of the N strongest kept groups into <out base>_cutouts.npz "
+                           "(implies --group).")
+    parser.add_option("--cutout-bins", type="int", default=256, metavar="N",
+                      help="Time bins of both images. (Default: 256)")
+    parser.add_option("--cutout-subbands", type="int", default=None, metavar="N",
+                      help="Subbands of the frequency-time image; divides the channels. "
+                           "(Default: 256, or all channels if that does not divide them)")
+    parser.add_option("--cutout-dms", type="int", default=256, metavar="N",
+                      help="Trial DMs of the DM-time image. (Default: 256)")
+    parser.add_option("--cutout-dm-half", type="float", default=None, metavar="DM",
+                      help="Half-range of the DM-time image's trial DMs. (Default: the "
+                           "candidate's DM, at least 10)")
     parser.add_option("-d", "--debug", action="store_true", default=False)
     options, args = parser.parse_args(argv)
     if len(args) != 1:
@@ -143,13 +167,22 @@ def main(argv=None):
     from pypulsar_amd.search import DEFAULT_WIDTHS, write_singlepulse
     widths = tuple(w for w in DEFAULT_WIDTHS if w <= options.maxwidth) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
+    if options.cutouts < 0:
+        parser.error("--cutouts expects a count")
+    mask = None
+    if options.cutouts and (options.maskfile or options.rfifind):
+        # (made once: the search and the cut-outs see the same masked data)
+        from pypulsar_amd.formats import filterbank
+        fb = filterbank.filterbank(args[0])
+        mask = get_mask(args[0], fb, options.maskfile, options.rfifind, options.block)
+        fb.close()
     cands = search_file(args[0], dms, options.downsamp, options.block, options.zero_dm,
                         options.threshold, widths, debug=options.debug,
-                        maskfile=options.maskfile, rfifind=options.rfifind)
+                        maskfile=options.maskfile, rfifind=options.rfifind, rfimask=mask)
     out = options.outname or os.path.splitext(args[0])[0] + ".singlepulse"
     write_singlepulse(cands, out)
     print("%d candidates -> %s" % (len(cands), out))
-    if options.group:
+    if options.group or options.cutouts:
         from pypulsar_amd.spgroup import SinglePulseGrouper, select, write_groups
         # (the merged list is grouped once; its rows are those of the DM grid)
         _, groups = SinglePulseGrouper(options.group_rows, options.group_samples)(cands, dms=dms)
@@ -158,6 +191,21 @@ def main(argv=None):
         write_groups(kept, gout)
         print("%d candidates -> %d groups -> %d kept -> %s"
               % (len(cands), len(groups), len(kept), gout))
+    if options.cutouts:
+        from pypulsar_amd.cutout import cutouts_from_file, write_cutouts
+        from pypulsar_amd.formats import filterbank
+        best = kept[np.argsort(-kept["Sigma"], kind="stable")[:options.cutouts]]
+        fb = filterbank.filterbank(args[0])
+        nsub = options.cutout_subbands
+        if nsub is None:
+            nsub = 256 if fb.nchans % 256 == 0 else fb.nchans
+        ft, dmt, jobs = cutouts_from_file(fb, best, options.downsamp, rfimask=mask,
+                                          nbin=options.cutout_bins, nsub=nsub,
+                                          ndm=options.cutout_dms, dm_half=options.cutout_dm_half)
+        fb.close()
+        cout = os.path.splitext(out)[0] + "_cutouts.npz"
+        write_cutouts(cout, ft, dmt, best, jobs)
+        print("%d cut-outs -> %s" % (len(best), cout))
     return 0
 
 
