@@ -570,6 +570,76 @@ int pdd_fold_search(const double* prof, const int32_t* cnt, const double* sumsq,
                     int npart, int nbins, int A, int B, double* chi2, int32_t* best,
                     double* best_chi2, double* best_prof, int32_t* best_cnt, void* stream);
 
+/* ---- folding of periodicity candidates from the raw block into (sub-
+ * integration, subband, phase) cubes and the DM refinement on such a cube
+ * (pypulsar_amd/subfold.py; restated by brute force in
+ * tests/subfold_oracle.py).
+ * x: DEVICE time-major block [n][C], row stride ld elements, PDD_U8 or
+ * PDD_F32 (the layout of pdd_cutout_*), whose first row is raw sample
+ * t_first of a file of N samples.  table: DEVICE int32 [rows][C] delay bins
+ * (delays.sweep_table at the raw dt, reference = the highest channel: every
+ * entry >= 0).  A job is 8 int64 {P0, step, accel, L, i0, i1, row, bmax}:
+ * the phase model of pdd_fold_rows (fold.phase_steps; f at raw sample 0),
+ * b[c] = table[row][c], bmax = max_c b[c], n_out = N - bmax the trimmed
+ * length of a single-DM sweep, L = n_out / npart.  Dedispersed sample
+ * i < npart L has P_i = P0 + i step + (i (i - 1) / 2) accel (mod 2^64) and
+ * bin(i) = ((P_i >> 32) * nbins) >> 32, shared by every channel; the rest is
+ * dropped as in pdd_fold_rows.  Subband s = channels s C/nsub ..
+ * (s+1) C/nsub - 1 in file order.  With p = i / L:
+ *   cube[j][p][s][bin(i)] += sum_{c in s} x[i + b[c]][c]        float64
+ *   cnt[j][p][bin(i)]     += 1   (per sample, not per channel)  int32
+ *   chansum[j][c] += x[i + b[c]][c],  chansq[j][c] += x^2       float64
+ * A call folds the samples i0 <= i < i1 of each job from the block it is
+ * given and ADDS to the outputs, which pdd_subfold_zero (or the caller)
+ * cleared: a file is folded block by block, consecutive blocks overlapping
+ * by bmax rows.  Promised per job, checked on the HOST copy before anything
+ * is launched: L >= 1, 0 <= i0 <= i1 <= npart L, 0 <= row < rows, and, where
+ * i0 < i1, t_first <= i0 and i1 - 1 + bmax < t_first + n.  The kernel guards
+ * every load: a job whose device table breaks bmax reads nothing outside the
+ * block (such samples count as 0; the result is unspecified).
+ * 8-bit input: integers on chip, then float64 adds of integers below 2^53:
+ * every output is the exact integer, bit-identical for any scheduling and
+ * any split into blocks.  float32 input: float64 sums in no fixed order.
+ * Limits (refused, -1): 2 <= nbins <= 256, 1 <= npart <= 128, npart nbins <=
+ * 8192, nsub nbins <= 8192, nsub divides C, n < 2^31, npart L < 2^31.  jobs:
+ * HOST copy, jobs_dev: the same J x 8 int64 on the device.  J == 0: no-op.
+ * tile_span: the largest (max - min) delay within any aligned group of 64
+ * consecutive channels of any job's table row, or -1 where unknown (bmax is
+ * taken): it only sizes the LDS in which 8-bit rows are staged; the kernel
+ * checks every tile's own span and reads per lane where it does not fit, so
+ * a wrong value costs time, never a result. */
+int pdd_subfold_zero(double* cube, int32_t* cnt, double* chansum, double* chansq, int64_t J,
+                     int64_t C, int npart, int nsub, int nbins, void* stream);
+int pdd_subfold(const void* x, int dtype, int64_t n, int64_t C, int64_t ld, int64_t t_first,
+                const int64_t* jobs, const int64_t* jobs_dev, int64_t J, const int32_t* table,
+                int64_t rows, int npart, int nsub, int nbins, double* cube, int32_t* cnt,
+                double* chansum, double* chansq, int64_t tile_span, void* stream);
+/* DM refinement of J cubes.  trials: DEVICE int32 [J][2] = (ia, ib); rtab:
+ * DEVICE int32 [J][ndm][nsub]; ntot: DEVICE int64 [J] = npart L.  Per job,
+ * with s_p = the shift of part p of pdd_fold_search's formula (fold.trial_shift):
+ *   sub[s][b] = sum_p cube[p][s][(b + s_p) mod nbins]   (ascending p),
+ *   Cb[b]     = the same sum over cnt,
+ *   subints[p][b] = sum_s cube[p][s][b]                 (ascending s, no shift),
+ *   mu_c = chansum[c] / Ntot, var_c = chansq[c] / Ntot - mu_c mu_c,
+ *   mu_s = sum_{c in s} mu_c, var_s = sum_{c in s} var_c (ascending c; 0 where Ntot = 0).
+ * Ladder entry k reads subband s r = rtab[k][s] mod nbins bins further on;
+ * with idx = (b + r) mod nbins and sums over ascending s:
+ *   S_k[b] = sum_s sub[s][idx], E_k[b] = sum_s mu_s Cb[idx], V_k[b] = sum_s var_s Cb[idx],
+ *   chi2[k] = (sum over b ascending, V_k[b] > 0, of (S_k[b] - E_k[b])^2 / V_k[b]) / (nbins - 1),
+ * all float64 without contraction.  (The host makes rtab[k][s] =
+ * floor((dms[k] - DM) u_s f nbins + 0.5) mod nbins, u_s the delay per unit DM
+ * of the subband's centre relative to the highest channel: subfold.ladder_shifts.)
+ * best[J]: the first k in the order (chi2 descending, |k - ndm / 2|
+ * ascending, k ascending); best_chi2[J]; best_prof[J][nbins] = S_best;
+ * best_cnt[J][nbins] int64 = sum_s Cb[idx] of the best entry (the (sample,
+ * subband) pairs behind S_best[b]).  chi2: [J][ndm], sub: [J][nsub][nbins],
+ * subints: [J][npart][nbins].  1 <= ndm <= 1024 and the limits of pdd_subfold. */
+int pdd_subfold_dm(const double* cube, const int32_t* cnt, const double* chansum,
+                   const double* chansq, const int64_t* ntot, const int32_t* trials,
+                   const int32_t* rtab, int64_t J, int64_t C, int npart, int nsub, int nbins,
+                   int ndm, double* chi2, int32_t* best, double* best_chi2, double* best_prof,
+                   int64_t* best_cnt, double* sub, double* subints, void* stream);
+
 /* ---- fast-folding (FFA) search of a DM-time plane for long periods
  * (pypulsar_amd/ffa.py; restated in tests/ffa_oracle.py).  A step of the plan
  * searches base periods p0 = b_lo .. b_hi - 1 bins on the series downsampled

@@ -56,6 +56,7 @@ EXPORTS = (
     "pdd_rfi_apply", "pdd_ffa_plan_info", "pdd_ffa_downsample", "pdd_ffa_detrend", "pdd_ffa_pass",
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
+    "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm",
 )
 
 
@@ -162,6 +163,11 @@ _SIGS = {
                        _vp, _vp], _int),
     "pdd_cutout_dmt": ([_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _int, _int, _int,
                         _i64, _vp, _i64, _vp, _vp], _int),
+    "pdd_subfold_zero": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _vp], _int),
+    "pdd_subfold": ([_vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _int, _int,
+                     _int, _vp, _vp, _vp, _vp, _i64, _vp], _int),
+    "pdd_subfold_dm": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int,
+                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _int),
 }
 
 

@@ -14,7 +14,11 @@ the host.  They are sifted across DMs and harmonics and written in the
 ``.accelcands`` layout.  With ``--fold K`` the K strongest sifted candidates
 are then folded on the plane (pypulsar_amd.fold: their own DM row and its
 neighbours, a search over period and period derivative) and written as
-``<base>_cand<k>.bestprof`` and ``<base>_cand<k>.npz``.  With ``--zmax Z`` the
+``<base>_cand<k>.bestprof`` and ``<base>_cand<k>.npz``; with
+``--fold-subbands NSUB`` each is also folded from the input file itself, at
+its own time resolution, into NSUB subbands and its DM refined on a ladder
+finer than the grid (pypulsar_amd.subfold): ``<base>_cand<k>_subbands.npz``
+holds the phase-versus-frequency image.  With ``--zmax Z`` the
 rows are searched for signals that drift up to Z Fourier bins over the
 observation (pulsars in binaries; pypulsar_amd.accel): the candidates carry
 their ``z``, and a fold starts from their frequency derivative.  With
@@ -30,6 +34,7 @@ periodicity or acceleration search.
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 --fold-subbands 32 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --autozap obs.fil
@@ -184,6 +189,16 @@ def main(argv=None):
                       help="Sub-integrations of a fold. (Default: 32)")
     parser.add_option("--fold-dm-halfwidth", dest="fold_dm_halfwidth", type="int", default=2,
                       help="DM trials folded on each side of a candidate's. (Default: 2)")
+    parser.add_option("--fold-subbands", dest="fold_subbands", type="int", default=0,
+                      metavar="NSUB",
+                      help="Also fold the K candidates of --fold from the input file into NSUB "
+                           "subbands at the file's own resolution and refine their DM on a "
+                           "ladder finer than the grid (the --mask / --rfifind mask applied, the "
+                           "zero-DM filter not); writes <base>_cand<k>_subbands.npz. "
+                           "(Default: 0, off)")
+    parser.add_option("--fold-ndm", dest="fold_ndm", type="int", default=None,
+                      help="Entries of the DM ladder of --fold-subbands. "
+                           "(Default: --fold-nbins + 1)")
     parser.add_option("--ffa", action="store_true", default=False,
                       help="Also run the fast-folding search for slow pulsars on the plane; "
                            "writes <base>.ffacands (and, with --fold K, "
@@ -211,6 +226,8 @@ def main(argv=None):
     from pypulsar_amd.periodicity import sift, write_accelcands
     if options.zmax < 0 or options.dz < 1:
         parser.error("--zmax must be >= 0 and --dz >= 1")
+    if options.fold_subbands < 0 or (options.fold_subbands and options.fold <= 0):
+        parser.error("--fold-subbands NSUB needs NSUB >= 0 and --fold K")
     numharm = min(options.numharm, 16) if options.zmax > 0 else options.numharm
     harms = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= numharm) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
@@ -234,9 +251,11 @@ def main(argv=None):
     write_accelcands(sifted, out, basename=os.path.basename(base), zmax=options.zmax)
     print("%d candidates (%d sifted) -> %s" % (len(cands), len(sifted), out))
     if options.fold > 0:
-        fold_candidates(res[2], dms, res[1], sifted[:options.fold], os.path.splitext(out)[0],
-                        args[0], options.fold_npart, options.fold_nbins,
-                        options.fold_dm_halfwidth)
+        folded = fold_candidates(res[2], dms, res[1], sifted[:options.fold],
+                                 os.path.splitext(out)[0], args[0], options.fold_npart,
+                                 options.fold_nbins, options.fold_dm_halfwidth)
+        if options.fold_subbands:
+            fold_subbands(folded, os.path.splitext(out)[0], args[0], options)
     if options.ffa:
         from pypulsar_amd.ffa import FFASearch
         fs = FFASearch(options.ffa_pmin, options.ffa_pmax, options.ffa_bins_min,
@@ -248,10 +267,38 @@ def main(argv=None):
         write_accelcands(fsifted, fout, basename=os.path.basename(base))
         print("%d FFA candidates (%d sifted) -> %s" % (len(fcands), len(fsifted), fout))
         if options.fold > 0:
-            fold_candidates(res[2], dms, res[1], fsifted[:options.fold], os.path.splitext(out)[0],
-                            args[0], options.fold_npart, options.fold_nbins,
-                            options.fold_dm_halfwidth, tag="ffacand")
+            folded = fold_candidates(res[2], dms, res[1], fsifted[:options.fold],
+                                     os.path.splitext(out)[0], args[0], options.fold_npart,
+                                     options.fold_nbins, options.fold_dm_halfwidth, tag="ffacand")
+            if options.fold_subbands:
+                fold_subbands(folded, os.path.splitext(out)[0], args[0], options, tag="ffacand")
     return 0
+
+
+def fold_subbands(folded, base, infile, options, tag="cand"):
+    """Fold the FoldedCandidates of ``fold_candidates`` from the input file
+    into ``options.fold_subbands`` subbands and refine their DM
+    (pypulsar_amd.subfold); the mask the search used (--mask, or the
+    <base>_rfifind.mask that --rfifind left) is applied.  Writes
+    ``<base>_<tag><k>_subbands.npz`` and prints one line per candidate."""
+    from pypulsar_amd.formats import filterbank
+    from pypulsar_amd.subfold import subfold_from_file, write_subfold
+    fb = filterbank.filterbank(infile)
+    mask = None
+    maskfile = os.path.splitext(infile)[0] + "_rfifind.mask" if options.rfifind else options.maskfile
+    if maskfile:
+        from pypulsar_amd import rfi
+        mask = rfi.mask_from_file(maskfile, fb)
+    folds = subfold_from_file(fb, folded, rfimask=mask, npart=options.fold_npart,
+                              nsub=options.fold_subbands, nbins=options.fold_nbins,
+                              ndm=options.fold_ndm)
+    fb.close()
+    for k, sf in enumerate(folds, 1):
+        name = "%s_%s%d_subbands.npz" % (base, tag, k)
+        write_subfold(name, sf)
+        print("%s %d subbands: fold DM %.2f  refined DM %.2f +- %.2f  reduced chi2 %.2f  "
+              "sigma %.1f -> %s" % (tag, k, sf.dm_fold, sf.dm, sf.ddm, sf.chi2, sf.sigma, name))
+    return folds
 
 
 def fold_candidates(plane, dms, dt, sifted, base, infile, npart=32, nbins=64, dm_halfwidth=2,
