@@ -147,6 +147,36 @@ int pdd_zdm_int_downsample(const void* in, int dtype, int64_t nspec, int64_t nch
                            int64_t factor, int mode, int offset, uint16_t* out, int64_t ld_out,
                            void* stream);
 
+/* ---- SIGPROC filterbanks packed below a byte (nbits 1, 2 or 4) ----
+ * Order within a byte is SIGPROC's: the first channel sits in the least
+ * significant bits (4 bits: low nibble first, as formats/psrfits.py
+ * unpack_4bit; 2 bits: fields at shifts 0, 2, 4, 6; 1 bit: bit 0 first).
+ * Parity of the 1- and 2-bit orders with a reference reader is unpinned
+ * (the reference reads neither). */
+/* The general path: time-major packed rows in[nspec] of nchan nbits / 8 bytes,
+ * ld_in_bytes apart -> time-major uint8 out[nspec][nchan] (rows ld_out apart),
+ * for every consumer of an 8-bit block.  Any nchan with nchan nbits % 8 == 0,
+ * any strides, nspec >= 0.  16 channels per thread (one 2 nbits-byte load,
+ * one 16-byte store) where nchan % 16 == 0 and both pointers and strides are
+ * aligned to those widths; one packed byte per thread otherwise. */
+int pdd_unpack_bits(const void* in, int nbits, int64_t nspec, int64_t nchan, int64_t ld_in_bytes,
+                    uint8_t* out, int64_t ld_out, void* stream);
+/* pdd_zdm_int_downsample reading packed rows (streaming configs[4] on 1-, 2-
+ * and 4-bit files): unpack + zero-DM + co-add by factor + corner turn in one
+ * pass, no 8-bit intermediate.  For every mode, factor and offset the output
+ * is bit for bit pdd_zdm_int_downsample's on the unpacked bytes: m is the
+ * spectrum's channel mean (double(sum) / double(nchan), the sum taken exactly
+ * over the bit fields) rounded half-to-even, PDD_ZDM_WRAP is mod 256 (uint8
+ * arithmetic on the unpacked array), the trailing partial group is dropped.
+ * Packed rows must be 16-byte aligned (in, ld_in_bytes and nchan nbits / 8
+ * multiples of 16); with vmax = 2^nbits - 1, offset + factor vmax (255 factor
+ * for PDD_ZDM_WRAP) <= 65535, and offset >= factor vmax for PDD_ZDM_INT.  For
+ * the 16-bit sweep (values <= 1023) 4-bit data allow factor <= 64 without a
+ * filter and <= 32 with PDD_ZDM_INT (offset 15 factor). */
+int pdd_zdm_packed_int_downsample(const void* in, int nbits, int64_t nspec, int64_t nchan,
+                                  int64_t ld_in_bytes, int64_t factor, int mode, int offset,
+                                  uint16_t* out, int64_t ld_out, void* stream);
+
 /* ---- waterfaller post-chain (Spectra.scaled / scaled2 / masked / smooth) ---- */
 /* Whole-array statistics of x[C][N] into out4 (device float[4]):
  * {mean, population std, min, max}, float64 accumulation.

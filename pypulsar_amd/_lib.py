@@ -56,7 +56,8 @@ EXPORTS = (
     "pdd_rfi_apply", "pdd_ffa_plan_info", "pdd_ffa_downsample", "pdd_ffa_detrend", "pdd_ffa_pass",
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
-    "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm",
+    "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm", "pdd_unpack_bits",
+    "pdd_zdm_packed_int_downsample",
 )
 
 
@@ -168,6 +169,9 @@ _SIGS = {
                      _int, _vp, _vp, _vp, _vp, _i64, _vp], _int),
     "pdd_subfold_dm": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int,
                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _int),
+    "pdd_unpack_bits": ([_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp], _int),
+    "pdd_zdm_packed_int_downsample": ([_vp, _int, _i64, _i64, _i64, _i64, _int, _int, _vp, _i64,
+                                       _vp], _int),
 }
 
 

@@ -46,15 +46,20 @@ def _chunks(fb, block, nbuf=4, start_block=0):
     """Pinned [n, nchans] host chunks of the file from block ``start_block``
     on, in rotation (a buffer is reused nbuf chunks later, after its
     asynchronous copy has completed: StreamingSweep keeps at most 2 chunks in
-    flight)."""
+    flight).  A 1-, 2- or 4-bit file is read as it is: packed
+    [n, bytes_per_spectrum] uint8 chunks, unpacked on the device."""
     import torch
     tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.int16,
            np.dtype(np.float32): torch.float32}[np.dtype(fb.dtype)]
-    bufs = [torch.empty((block, fb.nchans), dtype=tdt, pin_memory=True) for _ in range(nbuf)]
+    width = fb.bytes_per_spectrum if fb.packed else fb.nchans
+    bufs = [torch.empty((block, width), dtype=tdt, pin_memory=True) for _ in range(nbuf)]
     done, i = int(start_block) * block, 0
     while done < fb.number_of_samples:
         h = bufs[i % nbuf]
-        n = fb.read_block_into(done, h.numpy().view(np.dtype(fb.dtype))[:block])
+        if fb.packed:
+            n = fb.read_packed_into(done, h.numpy()[:block])
+        else:
+            n = fb.read_block_into(done, h.numpy().view(np.dtype(fb.dtype))[:block])
         if n <= 0:
             break
         yield h[:n]
@@ -94,7 +99,7 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
     ss = StreamingSearch(dms, fb.freqs, fb.tsamp, block=block, downsamp=downsamp,
                          zero_dm=zero_dm, dtype=tdt, threshold=threshold,
                          widths=widths or DEFAULT_WIDTHS, detrendlen=detrendlen,
-                         rfimask=rfimask if rfimask is not None else
+                         nbits=fb.nbits if fb.packed else 8, rfimask=rfimask if rfimask is not None else
                          get_mask(infile, fb, maskfile, rfifind, block))
     parts = []  # candidate times are relative to the file start
     for i, c in enumerate(ss(_chunks(fb, block))):

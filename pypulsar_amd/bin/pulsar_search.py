@@ -79,7 +79,15 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     assert 64 % downsamp == 0, "the downsampling factor must divide 64"
     C, dt = fb.nchans, fb.tsamp * downsamp
     n = fb.number_of_samples // downsamp * downsamp
-    raw = torch.from_numpy(fb.read_all_samples()[:n * C].reshape(n, C)).cuda()
+    if fb.packed:
+        # a 1-, 2- or 4-bit file: its bytes go to the device and are unpacked there
+        from pypulsar_amd.stream import unpack_bits
+        host = np.empty((n, fb.bytes_per_spectrum), dtype=np.uint8)
+        got = fb.read_packed_into(0, host)
+        assert got == n, "short read: %d of %d spectra" % (got, n)
+        raw = unpack_bits(torch.from_numpy(host).cuda(), fb.nbits, C)
+    else:
+        raw = torch.from_numpy(fb.read_all_samples()[:n * C].reshape(n, C)).cuda()
     if rfifind or maskfile:
         from pypulsar_amd import rfi
         if rfifind:

@@ -30,6 +30,11 @@ def filter_file(infile, outname, block=BLOCK, debug=False):
     from pypulsar_amd.formats import filterbank, sigproc
 
     fb = filterbank.filterbank(infile)
+    if fb.packed:
+        # the input header is copied onto the output: 8-bit values would be
+        # written under an nbits = 1/2/4 header
+        raise ValueError("zero_dm_filter: %d-bit packed input is not supported (packed output "
+                         "is not written); convert the file to 8 bits first" % fb.nbits)
     nchan = fb.nchans
     np_dtype = np.dtype(fb.dtype)
     tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.int16,

@@ -17,8 +17,15 @@ header format it implements:
 Parity with PRESTO's module itself is unpinned (no reference test or fixture
 holds a header); the codec is checked by round trips and by hand-built byte
 strings in tests/test_filterbank.py.
+
+``pack_bits`` / ``unpack_bits``: the sample codec of files packed below a byte
+(nbits 1, 2, 4).  The 4-bit order is pinned through psrfits.unpack_4bit; the
+1- and 2-bit orders are SIGPROC's documented ones, parity unpinned
+(tests/test_lowbit_host.py fixes them by hand-written bytes).
 """
 import struct
+
+import numpy as np
 
 INT_KEYS = ("telescope_id", "machine_id", "data_type", "barycentric", "pulsarcentric",
             "nbits", "nsamples", "nchans", "nifs", "nbeams", "ibeam")
@@ -108,6 +115,45 @@ def write_header(f, header_params, header):
     (bin/zero_dm_filter.py:21-27)."""
     for key in header_params:
         f.write(addto_hdr(key, header.get(key)))
+
+
+PACKED_NBITS = (1, 2, 4)
+
+
+def _check_packed_nbits(nbits):
+    if nbits not in PACKED_NBITS:
+        raise ValueError("packed nbits must be 1, 2 or 4, not %r" % (nbits,))
+    return int(nbits)
+
+
+def unpack_bits(packed, nbits):
+    """[n, C*nbits/8] uint8 bytes -> [n, C] uint8 values of ``nbits`` (1, 2 or
+    4) bits each.  Order within a byte is SIGPROC's: the first channel sits in
+    the least significant bits (4 bits: low nibble first, as
+    psrfits.unpack_4bit; 2 bits: fields at shifts 0, 2, 4, 6; 1 bit: bit 0
+    first)."""
+    nbits = _check_packed_nbits(nbits)
+    packed = np.asarray(packed, dtype=np.uint8)
+    shifts = np.arange(0, 8, nbits, dtype=np.uint8)
+    vals = (packed[..., None] >> shifts) & np.uint8((1 << nbits) - 1)
+    return vals.reshape(packed.shape[:-1] + (packed.shape[-1] * len(shifts),))
+
+
+def pack_bits(values, nbits):
+    """[n, C] uint8 values -> [n, C*nbits/8] uint8 bytes, the inverse of
+    ``unpack_bits``.  ValueError on a value that does not fit in ``nbits`` or
+    a row that does not fill whole bytes."""
+    nbits = _check_packed_nbits(nbits)
+    values = np.asarray(values)
+    per = 8 // nbits
+    if values.shape[-1] % per:
+        raise ValueError("pack_bits: %d values of %d bits do not fill whole bytes"
+                         % (values.shape[-1], nbits))
+    if values.size and (values.min() < 0 or values.max() >= (1 << nbits)):
+        raise ValueError("pack_bits: a value does not fit in %d bits" % nbits)
+    v = values.astype(np.uint8).reshape(values.shape[:-1] + (values.shape[-1] // per, per))
+    shifts = np.arange(0, 8, nbits, dtype=np.uint8)
+    return np.bitwise_or.reduce(v << shifts, axis=-1).astype(np.uint8)
 
 
 def make_header(nchans, nbits, tsamp, fch1, foff, tstart=60000.0, source_name="synthetic",

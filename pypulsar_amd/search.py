@@ -132,11 +132,14 @@ class StreamingSearch(object):
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm=True, dtype=None,
                  threshold=6.0, widths=DEFAULT_WIDTHS, detrendlen=1024, max_cands=1 << 20,
-                 rfimask=None):
+                 rfimask=None, nbits=8):
         from .stream import StreamingSweep
         kw = {} if dtype is None else {"dtype": dtype}
         if rfimask is not None:
             kw["rfimask"] = rfimask
+        if nbits != 8:
+            # chunks are packed rows, uint8 [n, C*nbits/8] (StreamingSweep)
+            kw["nbits"] = nbits
         self.sweep = StreamingSweep(dms, freqs, dt, block=block, downsamp=downsamp,
                                     zero_dm=zero_dm, **kw)
         self.search = SinglePulseSearch(threshold, widths, detrendlen, max_cands)

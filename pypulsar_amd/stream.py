@@ -18,6 +18,15 @@ taken in the data dtype):
     (the reference's semantics for float data).
   * ``False``: no filter (8-bit input, downsamp <= 4: exact 16-bit path).
 
+Packed input (``nbits`` 1, 2 or 4: chunks are uint8 [n, nchan*nbits/8] in
+SIGPROC bit order, and the raw buffers and copies below hold packed rows):
+without a mask, on 16-byte packed rows and with the image's bound <= 1023
+(``ds vmax`` for no filter, ``2 ds vmax`` for "int", ``255 ds`` for "wrap",
+vmax = 2**nbits - 1) the prologue is pdd_zdm_packed_int_downsample, unpack
+included; otherwise the block is unpacked (pdd_unpack_bits) into an 8-bit
+block that takes the 8-bit path.  ``"auto"`` is then ``"int"`` where its bound
+fits, else ``"float"`` (a uint8 wrap of 2-bit values is noise).
+
 Per input chunk (``block`` spectra of the stream, time-major [n, nchan] in
 file order, 8/16-bit or float32):
 
@@ -53,12 +62,34 @@ _CODES = {torch.uint8: _lib.U8, torch.int16: _lib.U16, torch.float32: _lib.F32}
 _ZDM = {"none": _lib.ZDM_NONE, "int": _lib.ZDM_INT, "wrap": _lib.ZDM_WRAP}
 
 
-def prologue(raw, n, C, ds, mode, img, offset=0, stream=None):
+def unpack_bits(packed, nbits, C, out=None, n=None, stream=None):
+    """Device unpack (pdd_unpack_bits) of the first ``n`` packed rows of
+    ``packed`` ([rows, >= C*nbits/8] uint8, time-major, SIGPROC bit order)
+    into the time-major uint8 block ``out[:n]`` ([rows, >= C]; made here when
+    None).  Returns out[:n, :C]."""
+    assert packed.dtype == torch.uint8 and packed.dim() == 2 and packed.stride(1) == 1
+    n = packed.shape[0] if n is None else int(n)
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.uint8, device=packed.device)
+    assert out.dtype == torch.uint8 and out.stride(1) == 1 and out.shape[0] >= n
+    assert packed.shape[0] >= n and out.shape[1] >= C and packed.shape[1] * 8 >= C * nbits
+    if n:
+        call("pdd_unpack_bits", ptr(packed), int(nbits), n, C, packed.stride(0), ptr(out),
+             out.stride(0), stream_ptr(stream))
+    return out[:n, :C]
+
+
+def prologue(raw, n, C, ds, mode, img, offset=0, stream=None, nbits=8):
     """zero-DM (``mode``) + downsample by ``ds`` + corner turn of the
     time-major block raw[:n] into the channel-major image ``img``: 16-bit
-    offset integers (pdd_zdm_int_downsample) when ``img`` is int16, float32
-    (pdd_zdm_downsample) otherwise."""
-    if img.dtype == torch.int16:
+    offset integers (pdd_zdm_int_downsample; with ``nbits`` 1, 2 or 4
+    pdd_zdm_packed_int_downsample on packed rows) when ``img`` is int16,
+    float32 (pdd_zdm_downsample) otherwise."""
+    if nbits != 8:
+        assert img.dtype == torch.int16, "packed rows feed the 16-bit image only"
+        call("pdd_zdm_packed_int_downsample", ptr(raw), int(nbits), n, C, raw.stride(0), ds,
+             _ZDM[mode], offset, ptr(img), img.stride(0), stream_ptr(stream))
+    elif img.dtype == torch.int16:
         call("pdd_zdm_int_downsample", ptr(raw), _lib.U8, n, C, raw.stride(0), ds, _ZDM[mode],
              offset, ptr(img), img.stride(0), stream_ptr(stream))
     else:
@@ -73,8 +104,14 @@ class StreamingSweep(object):
     (downsampled time index)."""
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm="auto",
-                 dtype=torch.uint8, device="cuda", rfimask=None):
+                 dtype=torch.uint8, device="cuda", rfimask=None, nbits=8):
         _lib.require_gpu()
+        # nbits 1, 2 or 4: chunks are packed rows, host uint8 [n, C*nbits/8]
+        # (SIGPROC bit order), unpacked on the device
+        if nbits not in (1, 2, 4, 8):
+            raise ValueError("nbits must be 1, 2, 4 or 8")
+        self.nbits = int(nbits)
+        self.packed = self.nbits < 8
         # rfimask: a pypulsar_amd.rfi.RFIMask applied in place to every raw
         # block (at its absolute start sample) just before the prologue
         self.rfimask = rfimask
@@ -86,8 +123,35 @@ class StreamingSweep(object):
         self.C = len(self.freqs)
         self.ds = int(downsamp)
         self.dt = dt
+        if self.packed:
+            assert dtype == torch.uint8, "packed input unpacks to 8-bit values"
+            if (self.C * self.nbits) % 8:
+                raise ValueError("%d channels of %d bits do not fill whole bytes"
+                                 % (self.C, self.nbits))
+        self.row_bytes = self.C * self.nbits // 8 if self.packed else self.C
+        vmax = (1 << self.nbits) - 1
+
+        def fused_bound(m):
+            # bound of the 16-bit image of the fused packed prologue (None:
+            # that path does not apply): co-added values for "none", offset
+            # ds vmax + co-added (x - round(mean)) for "int", co-added bytes
+            # of the uint8 wrap for "wrap"
+            if not self.packed or rfimask is not None or self.row_bytes % 16:
+                return None
+            return {"none": vmax, "int": 2 * vmax, "wrap": 255}.get(m, 1 << 20) * self.ds
+
+        def exact8(m):
+            # the exact 16-bit path of 8-bit blocks: 16-B rows, values <= 1023
+            return (dtype == torch.uint8 and m != "float" and self.C % 16 == 0
+                    and self.ds <= (2 if m == "int" else 4))
+
         mode = {True: "float", False: "none"}.get(zero_dm, zero_dm)
-        if mode == "auto":
+        if mode == "auto" and self.packed:
+            # no reference semantics for packed data (a uint8 wrap of 2-bit
+            # values is noise): the exact integer filter where its bound fits
+            fbi = fused_bound("int")
+            mode = "int" if (fbi is not None and fbi <= 1023) or exact8("int") else "float"
+        elif mode == "auto":
             # the reference's own result for 8-bit data: uint8 wrap
             # (zero_dm_filter.py:30-39), exact on the 16-bit path
             mode = "wrap" if (dtype == torch.uint8 and self.C % 16 == 0 and self.ds <= 4) else "float"
@@ -95,18 +159,31 @@ class StreamingSweep(object):
             raise ValueError("zero_dm must be 'auto', 'int', 'wrap', 'float', True or False")
         self.dtype = dtype
         self.device = torch.device(device)
+        # packed input, fused path: pdd_zdm_packed_int_downsample -> the u16
+        # sweep (no mask, 16-B packed rows, values <= 1023); otherwise packed
+        # blocks are unpacked (pdd_unpack_bits) and take the 8-bit path below
+        fb = fused_bound(mode)
+        self.fused = fb is not None and fb <= 1023
         # the exact 16-bit path: 8-bit input, 16-B rows, co-added values <= 1023
-        self.exact = (dtype == torch.uint8 and mode != "float" and self.C % 16 == 0
-                      and self.ds <= (2 if mode == "int" else 4))
+        self.exact = self.fused or exact8(mode)
         if mode in ("int", "wrap") and not self.exact:
+            if self.packed:
+                raise ValueError("zero_dm=%r on %d-bit input needs values <= 1023 on 16-byte "
+                                 "packed rows without a mask, or the 8-bit path's nchan %% 16 "
+                                 "== 0 and downsamp <= %d" % (mode, self.nbits,
+                                                              2 if mode == "int" else 4))
             raise ValueError("zero_dm=%r needs 8-bit input, nchan %% 16 == 0 and downsamp <= %d"
                              % (mode, 2 if mode == "int" else 4))
         self.mode = mode
         self.zero_dm = mode != "none"
-        self.offset = 255 * self.ds if mode == "int" else 0
-        # bound of the 16-bit image: offset + co-added (x - round(mean)) for
-        # "int" (<= 510 ds), co-added bytes for "wrap" / "none" (<= 255 ds)
-        self.input_max = (510 if mode == "int" else 255) * self.ds if self.exact else None
+        if self.fused:
+            self.offset = vmax * self.ds if mode == "int" else 0
+            self.input_max = fb
+        else:
+            self.offset = 255 * self.ds if mode == "int" else 0
+            # bound of the 16-bit image: offset + co-added (x - round(mean)) for
+            # "int" (<= 510 ds), co-added bytes for "wrap" / "none" (<= 255 ds)
+            self.input_max = (510 if mode == "int" else 255) * self.ds if self.exact else None
         self.sweep = DMSweep(dms, self.freqs, dt * self.ds, dtype="u16" if self.exact else "f32",
                              input_max=self.input_max)
         self.D = self.sweep.D
@@ -116,8 +193,11 @@ class StreamingSweep(object):
         assert self.ov <= self.block, "block must hold the overlap (max delay x downsamp)"
         n_raw = self.block + self.ov
         self.nbuf = 3
-        self.raw = [torch.empty((n_raw, self.C), dtype=dtype, device=self.device)
+        self.raw = [torch.empty((n_raw, self.row_bytes), dtype=dtype, device=self.device)
                     for _ in range(self.nbuf)]
+        # the 8-bit block of a packed stream off the fused path
+        self.unpacked = (torch.empty((n_raw, self.C), dtype=torch.uint8, device=self.device)
+                         if self.packed and not self.fused else None)
         self.img = torch.empty((self.C, n_raw // self.ds),
                                dtype=torch.int16 if self.exact else torch.float32,
                                device=self.device)
@@ -135,6 +215,9 @@ class StreamingSweep(object):
     def _process(self, raw, n_valid, out=None, s0=0):
         """zero-DM + downsample + sweep of raw[:n_valid] -> plane (trim=True);
         s0: the block's first input sample (for the RFI mask)."""
+        if self.unpacked is not None:
+            unpack_bits(raw, self.nbits, self.C, self.unpacked, n_valid)
+            raw = self.unpacked
         if self.rfimask is not None:
             self.rfimask.apply(raw[:n_valid], s0)
         nd = n_valid // self.ds
@@ -143,12 +226,14 @@ class StreamingSweep(object):
             out = torch.empty((self.D, max(n_out, 0)), dtype=torch.float32, device=self.device)
         if n_out == 0:
             return out[:, :0]
-        prologue(raw, n_valid, self.C, self.ds, self.mode, self.img, self.offset)
+        prologue(raw, n_valid, self.C, self.ds, self.mode, self.img, self.offset,
+                 nbits=self.nbits if self.fused else 8)
         self.sweep(self.img[:, :nd], trim=True, out=out, out_bias=-float(self.offset * self.C))
         return out[:, :n_out]
 
     def __call__(self, chunks, planes=None, start_block=0):
-        """chunks: iterable of host tensors [n, C] (pinned for an asynchronous
+        """chunks: iterable of host tensors [n, C] (packed input: uint8
+        [n, C*nbits/8]; pinned for an asynchronous
         copy; every chunk but the last must hold exactly ``block`` spectra).
         planes: optional list of preallocated [D, block/ds] device planes,
         used in rotation by EMITTED-block count (block j -> planes[j % len]),
@@ -168,7 +253,7 @@ class StreamingSweep(object):
         for i, chunk in enumerate(chunks):
             b = i % self.nbuf
             n = chunk.shape[0]
-            assert chunk.shape[1] == self.C and n <= self.block
+            assert chunk.shape[1] == self.row_bytes and n <= self.block
             head = min(self.ov, n)
             self.copy_stream.wait_event(self.free[b])
             with torch.cuda.stream(self.copy_stream):
