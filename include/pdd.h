@@ -785,6 +785,31 @@ int pdd_psrfits_subints(const uint8_t* raw, int64_t nsub, int64_t row_bytes, int
                         int nbits, int64_t nsblk, int64_t nchan, const float* wso, int64_t s0,
                         int64_t N, int flip, float* out, int64_t ld_out, void* stream);
 
+/* ---- PSRFITS search-mode subints -> the stream's time-major raw block
+ * out[n][nchan] (rows ld_out elements apart), channels in file order, no band
+ * flip.  rows: nsub consecutive SUBINT table rows as stored (row_bytes each,
+ * big-endian); DATA, [nsblk][npol][nchan] samples of nbits 4 (low nibble
+ * first) / 8 (uint8) / 16 (int16) / 32 (float32), starts data_off bytes into
+ * a row; scl_off, offs_off, wts_off are the byte offsets of DAT_SCL and
+ * DAT_OFFS ([npol][nchan] float32) and DAT_WTS ([nchan] float32) in a row,
+ * read from the rows themselves, or -1: not applied (1, 0, 1).  Output row
+ * j < n is sample g = s0 + j of the concatenated subints (subint g / nsblk,
+ * spectrum g % nsblk).
+ *   PDD_F32: ((v scl[c]) + offs[c]) wts[c] in float32, in that order, of
+ *     polarisation pol0 (bit for bit pdd_psrfits_subints' values); npol_sum
+ *     == 2: (((v0 scl0[c]) + offs0[c]) + ((v1 scl1[c]) + offs1[c])) wts[c]
+ *     of polarisations pol0 and pol0 + 1.
+ *   PDD_U8: v where wts[c] != 0 (or weights are not applied), else 0; only
+ *     with nbits <= 8, npol_sum == 1 and scl_off == offs_off == -1.
+ * Refused (non-zero, nothing written): null pointers, another nbits, 4-bit
+ * with odd npol nchan, s0 + n > nsub nsblk, a column running past row_bytes,
+ * pol0 + npol_sum > npol, ld_out < nchan, PDD_U8 outside its conditions.
+ * n == 0 returns 0 and writes nothing. */
+int pdd_psrfits_block(const uint8_t* rows, int64_t nsub, int64_t row_bytes, int64_t data_off,
+                      int64_t scl_off, int64_t offs_off, int64_t wts_off, int nbits, int64_t nsblk,
+                      int64_t nchan, int npol, int pol0, int npol_sum, int64_t s0, int64_t n,
+                      int out_code, void* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

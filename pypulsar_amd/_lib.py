@@ -57,7 +57,7 @@ EXPORTS = (
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
     "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm", "pdd_unpack_bits",
-    "pdd_zdm_packed_int_downsample",
+    "pdd_zdm_packed_int_downsample", "pdd_psrfits_block",
 )
 
 
@@ -135,6 +135,8 @@ _SIGS = {
                        _vp, _int, ctypes.c_float, _vp, _i64, _vp, _vp], _int),
     "pdd_psrfits_subints": ([_vp, _i64, _i64, _i64, _int, _i64, _i64, _vp, _i64, _i64, _int, _vp,
                              _i64, _vp], _int),
+    "pdd_psrfits_block": ([_vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _i64, _i64, _int, _int,
+                           _int, _i64, _i64, _int, _vp, _i64, _vp], _int),
     "pdd_ps_prep": ([_vp, _i64, _i64, _i64, _i64, _vp, _vp], _int),
     "pdd_ps_block_medians": ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp], _int),
     "pdd_ps_normalise": ([_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp], _int),

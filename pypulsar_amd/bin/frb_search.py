@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""frb_search.py -- streaming single-pulse search of a SIGPROC filterbank.
+"""frb_search.py -- streaming single-pulse search of a SIGPROC filterbank or
+PSRFITS search-mode file.
 
 New (the reference has no search; BASELINE config 5 plus its consumer):
 blocks of spectra are read into rotating pinned host buffers
@@ -13,10 +14,16 @@ file's DM-time plane.  Output: PRESTO-style ``.singlepulse`` text.
 
     python -m pypulsar_amd.bin.frb_search --lodm 0 --hidm 1000 --numdms 2048 \\
         --downsamp 2 --threshold 7 -o obs.singlepulse obs.fil
+    python -m pypulsar_amd.bin.frb_search --hidm 1000 --numdms 2048 guppi_obs_0001.fits
     python -m pypulsar_amd.bin.frb_search --rfifind 2.0 --numdms 2048 obs.fil
     python -m pypulsar_amd.bin.frb_search --mask obs_rfifind.mask --numdms 2048 obs.fil
     python -m pypulsar_amd.bin.frb_search --group --min-members 3 --min-group-dm 5 obs.fil
     python -m pypulsar_amd.bin.frb_search --cutouts 20 --min-members 3 obs.fil
+
+A PSRFITS file (recognised by content) is streamed as its own SUBINT rows,
+decoded on the device (pdd_psrfits_block; formats.psrfits.PsrfitsSearchFile):
+``--noscales``, ``--nooffsets``, ``--noweights`` and ``--poln K`` choose what
+the decode applies; they are ignored, with a note, for a filterbank.
 
 ``--mask`` / ``--rfifind``: the cells of an rfifind ``.mask`` (read, or made in
 a first pass over the file: pypulsar_amd.rfi) are replaced on the device by
@@ -47,8 +54,26 @@ def _chunks(fb, block, nbuf=4, start_block=0):
     on, in rotation (a buffer is reused nbuf chunks later, after its
     asynchronous copy has completed: StreamingSweep keeps at most 2 chunks in
     flight).  A 1-, 2- or 4-bit file is read as it is: packed
-    [n, bytes_per_spectrum] uint8 chunks, unpacked on the device."""
+    [n, bytes_per_spectrum] uint8 chunks, unpacked on the device.  A PSRFITS
+    file yields row chunks: the SUBINT rows [k, NAXIS1] of each block's
+    samples as stored (a seam row is read into both chunks), for
+    StreamingSweep(decoder=fb.decoder())."""
     import torch
+    if hasattr(fb, "read_rows_into"):
+        dec = fb.decoder()
+        bufs = [torch.empty((dec.max_rows(block), fb.row_bytes), dtype=torch.uint8,
+                            pin_memory=True) for _ in range(nbuf)]
+        done, i = int(start_block) * block, 0
+        while done < fb.number_of_samples:
+            h = bufs[i % nbuf]
+            row0, nrows, _ = dec.rows_for(done, block)
+            got = fb.read_rows_into(row0, h.numpy()[:nrows])
+            if got != nrows:
+                raise IOError("%s: short read, %d of %d rows" % (fb.filename, got, nrows))
+            yield h[:nrows]
+            done += block
+            i += 1
+        return
     tdt = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.int16,
            np.dtype(np.float32): torch.float32}[np.dtype(fb.dtype)]
     width = fb.bytes_per_spectrum if fb.packed else fb.nchans
@@ -67,13 +92,13 @@ def _chunks(fb, block, nbuf=4, start_block=0):
         i += 1
 
 
-def get_mask(infile, fb, maskfile=None, rfifind=None, block=1 << 18):
+def get_mask(infile, fb, maskfile=None, rfifind=None, block=1 << 18, file_kw=None):
     """The pypulsar_amd.rfi.RFIMask of a search: made in a first pass over the
     file with intervals of ``rfifind`` seconds (and left beside it as
     <base>_rfifind.mask), or read from ``maskfile``; None without either."""
     if rfifind:
         from pypulsar_amd.bin.rfifind import find_mask
-        mask = find_mask(infile, rfifind, block)
+        mask = find_mask(infile, rfifind, block, file_kw=file_kw)
         out = os.path.splitext(infile)[0] + "_rfifind.mask"
         mask.write(out)
         print("rfifind: %.2f%% masked -> %s" % (100.0 * mask.masked_fraction, out))
@@ -86,13 +111,14 @@ def get_mask(infile, fb, maskfile=None, rfifind=None, block=1 << 18):
 
 def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=6.0,
                 widths=None, detrendlen=1024, debug=False, maskfile=None, rfifind=None,
-                rfimask=None):
-    """``rfimask``: a mask already made (else ``maskfile`` / ``rfifind``)."""
+                rfimask=None, file_kw=None):
+    """``rfimask``: a mask already made (else ``maskfile`` / ``rfifind``);
+    ``file_kw``: open_search_file's keywords (PSRFITS input)."""
     import torch
-    from pypulsar_amd.formats import filterbank
+    from pypulsar_amd.formats.psrfits import open_search_file
     from pypulsar_amd.search import DEFAULT_WIDTHS, StreamingSearch, merge
 
-    fb = filterbank.filterbank(infile)
+    fb = open_search_file(infile, **(file_kw or {}))
     if np.dtype(fb.dtype) == np.uint16:
         raise ValueError("16-bit filterbanks: convert to 8 or 32 bits first")
     tdt = torch.uint8 if np.dtype(fb.dtype) == np.uint8 else torch.float32
@@ -100,7 +126,8 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
                          zero_dm=zero_dm, dtype=tdt, threshold=threshold,
                          widths=widths or DEFAULT_WIDTHS, detrendlen=detrendlen,
                          nbits=fb.nbits if fb.packed else 8, rfimask=rfimask if rfimask is not None else
-                         get_mask(infile, fb, maskfile, rfifind, block))
+                         get_mask(infile, fb, maskfile, rfifind, block, file_kw),
+                         decoder=fb.decoder() if hasattr(fb, "decoder") else None)
     parts = []  # candidate times are relative to the file start
     for i, c in enumerate(ss(_chunks(fb, block))):
         parts.append(c)
@@ -113,10 +140,18 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
     return merge(parts)
 
 
+def file_options(options):
+    """open_search_file's keywords from the parsed --noscales / --nooffsets /
+    --noweights / --poln options."""
+    return dict(apply_scales=options.apply_scales, apply_offsets=options.apply_offsets,
+                apply_weights=options.apply_weights, poln=options.poln)
+
+
 def main(argv=None):
     parser = optparse.OptionParser(prog="frb_search.py", usage="%prog [OPTIONS] INFILE",
                                    description="Streaming dedispersion + single-pulse search "
-                                               "of a SIGPROC filterbank on the GPU.")
+                                               "of a SIGPROC filterbank or PSRFITS search-mode "
+                                               "file on the GPU.")
     parser.add_option("--lodm", type="float", default=0.0, help="Lowest DM (pc/cc).")
     parser.add_option("--hidm", type="float", default=1000.0, help="Highest DM (pc/cc).")
     parser.add_option("--numdms", type="int", default=1024, help="Number of DM trials.")
@@ -165,10 +200,20 @@ def main(argv=None):
     parser.add_option("--cutout-dm-half", type="float", default=None, metavar="DM",
                       help="Half-range of the DM-time image's trial DMs. (Default: the "
                            "candidate's DM, at least 10)")
+    parser.add_option("--noscales", dest="apply_scales", action="store_false", default=True,
+                      help="PSRFITS input: do not apply DAT_SCL.")
+    parser.add_option("--nooffsets", dest="apply_offsets", action="store_false", default=True,
+                      help="PSRFITS input: do not apply DAT_OFFS.")
+    parser.add_option("--noweights", dest="apply_weights", action="store_false", default=True,
+                      help="PSRFITS input: do not apply DAT_WTS.")
+    parser.add_option("--poln", type="int", default=None, metavar="K",
+                      help="PSRFITS input: use polarisation K alone. (Default: the one "
+                           "polarisation, AA + BB of AABB data, I of IQUV)")
     parser.add_option("-d", "--debug", action="store_true", default=False)
     options, args = parser.parse_args(argv)
     if len(args) != 1:
-        parser.error("one input filterbank expected")
+        parser.error("one input file expected")
+    file_kw = file_options(options)
     from pypulsar_amd.search import DEFAULT_WIDTHS, write_singlepulse
     widths = tuple(w for w in DEFAULT_WIDTHS if w <= options.maxwidth) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
@@ -177,13 +222,14 @@ def main(argv=None):
     mask = None
     if options.cutouts and (options.maskfile or options.rfifind):
         # (made once: the search and the cut-outs see the same masked data)
-        from pypulsar_amd.formats import filterbank
-        fb = filterbank.filterbank(args[0])
-        mask = get_mask(args[0], fb, options.maskfile, options.rfifind, options.block)
+        from pypulsar_amd.formats.psrfits import open_search_file
+        fb = open_search_file(args[0], **file_kw)
+        mask = get_mask(args[0], fb, options.maskfile, options.rfifind, options.block, file_kw)
         fb.close()
     cands = search_file(args[0], dms, options.downsamp, options.block, options.zero_dm,
                         options.threshold, widths, debug=options.debug,
-                        maskfile=options.maskfile, rfifind=options.rfifind, rfimask=mask)
+                        maskfile=options.maskfile, rfifind=options.rfifind, rfimask=mask,
+                        file_kw=file_kw)
     out = options.outname or os.path.splitext(args[0])[0] + ".singlepulse"
     write_singlepulse(cands, out)
     print("%d candidates -> %s" % (len(cands), out))
@@ -198,9 +244,9 @@ def main(argv=None):
               % (len(cands), len(groups), len(kept), gout))
     if options.cutouts:
         from pypulsar_amd.cutout import cutouts_from_file, write_cutouts
-        from pypulsar_amd.formats import filterbank
+        from pypulsar_amd.formats.psrfits import open_search_file
         best = kept[np.argsort(-kept["Sigma"], kind="stable")[:options.cutouts]]
-        fb = filterbank.filterbank(args[0])
+        fb = open_search_file(args[0], **file_kw)
         nsub = options.cutout_subbands
         if nsub is None:
             nsub = 256 if fb.nchans % 256 == 0 else fb.nchans

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""pulsar_search.py -- periodicity search of a SIGPROC filterbank.
+"""pulsar_search.py -- periodicity search of a SIGPROC filterbank or PSRFITS
+search-mode file.
 
 New (the reference has no search; it reads PRESTO's ``.fft`` and
 ``.accelcands`` files, formats/prestofft.py and formats/accelcands.py): the
@@ -25,7 +26,12 @@ their ``z``, and a fold starts from their frequency derivative.  With
 ``--ffa`` the plane is also searched by fast folding (pypulsar_amd.ffa: slow,
 narrow pulses that the harmonic sums lose); its sifted candidates go to
 ``<base>.ffacands`` in the same layout, and ``--fold K`` folds its K strongest
-as ``<base>_ffacand<k>``.  With ``--zaplist FILE`` and / or ``--autozap`` the
+as ``<base>_ffacand<k>``.  A PSRFITS file (recognised by content) goes up as
+its own SUBINT rows and is decoded on the device in bounded pieces
+(pdd_psrfits_block);
+``--noscales``, ``--nooffsets``, ``--noweights`` and ``--poln K`` choose what
+the decode applies (ignored, with a note, for a filterbank).  With
+``--zaplist FILE`` and / or ``--autozap`` the
 Fourier bins of periodic interference -- listed in a PRESTO ``.zaplist``, or
 found on the plane as the bins that stand out in (nearly) every DM row
 (pypulsar_amd.zap) -- are set to the whitened mean level before the
@@ -33,6 +39,7 @@ periodicity or acceleration search.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 guppi_obs_0001.fits
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 --fold-subbands 32 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
@@ -53,7 +60,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
                 nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2, maskfile=None,
-                rfifind=None, zaplist=None, autozap=None):
+                rfifind=None, zaplist=None, autozap=None, file_kw=None):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
     pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
@@ -66,20 +73,24 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     ``autozap`` (a ``pypulsar_amd.zap.BirdieFinder``, or True for the default
     one, run on the swept plane; its list is left as <base>.zaplist): the
     Fourier bins of those intervals are set to the whitened mean level in
-    every DM row before the search; both: the two lists merged."""
+    every DM row before the search; both: the two lists merged.
+    ``file_kw``: open_search_file's keywords (PSRFITS input)."""
     import torch
-    from pypulsar_amd.formats import filterbank
+    from pypulsar_amd.formats.psrfits import open_search_file
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
     from pypulsar_amd.stream import prologue
     from pypulsar_amd.sweep import DMSweep
 
-    fb = filterbank.filterbank(infile)
+    fb = open_search_file(infile, **(file_kw or {}))
     if np.dtype(fb.dtype) == np.uint16:
         raise ValueError("16-bit filterbanks: convert to 8 or 32 bits first")
     assert 64 % downsamp == 0, "the downsampling factor must divide 64"
     C, dt = fb.nchans, fb.tsamp * downsamp
     n = fb.number_of_samples // downsamp * downsamp
-    if fb.packed:
+    if hasattr(fb, "read_device"):
+        # a PSRFITS file: its rows go to the device and are decoded there
+        raw = fb.read_device(0, n)
+    elif fb.packed:
         # a 1-, 2- or 4-bit file: its bytes go to the device and are unpacked there
         from pypulsar_amd.stream import unpack_bits
         host = np.empty((n, fb.bytes_per_spectrum), dtype=np.uint8)
@@ -140,7 +151,8 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
 def main(argv=None):
     parser = optparse.OptionParser(prog="pulsar_search.py", usage="%prog [OPTIONS] INFILE",
                                    description="Dedispersion + periodicity search of a SIGPROC "
-                                               "filterbank on the GPU.")
+                                               "filterbank or PSRFITS search-mode file on the "
+                                               "GPU.")
     parser.add_option("--lodm", type="float", default=0.0, help="Lowest DM (pc/cc).")
     parser.add_option("--hidm", type="float", default=100.0, help="Highest DM (pc/cc).")
     parser.add_option("--numdms", type="int", default=128, help="Number of DM trials.")
@@ -226,11 +238,22 @@ def main(argv=None):
     parser.add_option("--ffa-detrend", dest="ffa_detrend", type="float", default=None,
                       help="Length in s of the chunks whose means make the removed baseline. "
                            "(Default: 4 x --ffa-pmax)")
+    parser.add_option("--noscales", dest="apply_scales", action="store_false", default=True,
+                      help="PSRFITS input: do not apply DAT_SCL.")
+    parser.add_option("--nooffsets", dest="apply_offsets", action="store_false", default=True,
+                      help="PSRFITS input: do not apply DAT_OFFS.")
+    parser.add_option("--noweights", dest="apply_weights", action="store_false", default=True,
+                      help="PSRFITS input: do not apply DAT_WTS.")
+    parser.add_option("--poln", type="int", default=None, metavar="K",
+                      help="PSRFITS input: use polarisation K alone. (Default: the one "
+                           "polarisation, AA + BB of AABB data, I of IQUV)")
     parser.add_option("-o", "--outname", default=None,
                       help="Output .accelcands file (default: INFILE with .accelcands).")
     options, args = parser.parse_args(argv)
     if len(args) != 1:
-        parser.error("one input filterbank expected")
+        parser.error("one input file expected")
+    from pypulsar_amd.bin.frb_search import file_options
+    options.file_kw = file_options(options)
     from pypulsar_amd.periodicity import sift, write_accelcands
     if options.zmax < 0 or options.dz < 1:
         parser.error("--zmax must be >= 0 and --dz >= 1")
@@ -251,7 +274,7 @@ def main(argv=None):
                       return_plane=options.fold > 0 or options.ffa, zmax=options.zmax,
                       dz=options.dz,
                       maskfile=options.maskfile, rfifind=options.rfifind,
-                      zaplist=options.zaplist, autozap=finder)
+                      zaplist=options.zaplist, autozap=finder, file_kw=options.file_kw)
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]
@@ -289,9 +312,9 @@ def fold_subbands(folded, base, infile, options, tag="cand"):
     (pypulsar_amd.subfold); the mask the search used (--mask, or the
     <base>_rfifind.mask that --rfifind left) is applied.  Writes
     ``<base>_<tag><k>_subbands.npz`` and prints one line per candidate."""
-    from pypulsar_amd.formats import filterbank
+    from pypulsar_amd.formats.psrfits import open_search_file
     from pypulsar_amd.subfold import subfold_from_file, write_subfold
-    fb = filterbank.filterbank(infile)
+    fb = open_search_file(infile, **(getattr(options, "file_kw", None) or {}))
     mask = None
     maskfile = os.path.splitext(infile)[0] + "_rfifind.mask" if options.rfifind else options.maskfile
     if maskfile:

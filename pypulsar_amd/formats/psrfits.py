@@ -23,6 +23,14 @@ calendar formula (``_cldj``); ``get_spectra`` at the exact end of a file
 reads only the subints it needs (the reference indexes one past the last
 subint there and raises); multi-polarisation data (NPOL > 1 unsummed) is
 rejected as in the reference's reshape.
+
+New, for the searches: ``PsrfitsSearchFile`` gives a
+search-mode file the attributes and ``read_block_into`` of a ``filterbank``
+and streams it as its own SUBINT rows (``rows_for``, ``read_rows_into``),
+which ``PsrfitsDecoder`` turns into the stream's time-major uint8 or float32
+block on the device (``pdd_psrfits_block``: scales, offsets and weights read
+from the rows, one polarisation or AA + BB); ``open_search_file`` returns a
+``filterbank`` or a ``PsrfitsSearchFile`` by the file's content.
 """
 import os
 import re
@@ -458,35 +466,330 @@ class PsrfitsFile(object):
                                     starttime=self.tsamp * startsamp)
 
 
+class PsrfitsDecoder(object):
+    """Device decode of verbatim SUBINT rows into the stream's time-major raw
+    block (pdd_psrfits_block): what ``StreamingSweep(decoder=...)`` uses.
+    Holds the file's geometry only, no open file."""
+
+    def __init__(self, row_bytes, data_off, scl_off, offs_off, wts_off, nbits, nsblk, nchan,
+                 npol, pol0, npol_sum, nsubints, dtype):
+        self.row_bytes, self.data_off = int(row_bytes), int(data_off)
+        self.scl_off, self.offs_off, self.wts_off = int(scl_off), int(offs_off), int(wts_off)
+        self.nbits, self.nsblk, self.nchan = int(nbits), int(nsblk), int(nchan)
+        self.npol, self.pol0, self.npol_sum = int(npol), int(pol0), int(npol_sum)
+        self.nsubints = int(nsubints)
+        self.number_of_samples = self.nsubints * self.nsblk
+        self.dtype = np.dtype(dtype)  # uint8 (integer mode) or float32
+
+    @property
+    def torch_dtype(self):
+        import torch
+        return torch.uint8 if self.dtype == np.uint8 else torch.float32
+
+    def rows_for(self, start, n):
+        """(row0, nrows, s0): the rows that hold samples [start, start + n)
+        (cut at the end of the file) and the offset of ``start`` in the first
+        of them."""
+        start = int(start)
+        n = max(0, min(int(n), self.number_of_samples - start))
+        row0 = start // self.nsblk
+        s0 = start - row0 * self.nsblk
+        if n == 0:
+            return row0, 0, s0
+        return row0, (start + n - 1) // self.nsblk - row0 + 1, s0
+
+    def max_rows(self, n):
+        """Most rows any span of ``n`` samples touches."""
+        return (max(int(n), 1) - 1) // self.nsblk + 2
+
+    def decode(self, rows, nrows, s0, n, out, stream=None):
+        """Samples [s0, s0 + n) of the ``nrows`` device rows ``rows``
+        (uint8 [>= nrows, row_bytes]) -> out[:n] (device [>= n, >= nchan] of
+        this decoder's dtype, unit channel stride)."""
+        from .. import _lib
+        from .._lib import call, ptr, stream_ptr
+        assert rows.is_cuda and rows.dtype.itemsize == 1 and rows.is_contiguous()
+        assert rows.shape[1] == self.row_bytes and rows.shape[0] >= nrows
+        assert out.is_cuda and out.dtype == self.torch_dtype and out.stride(1) == 1
+        assert out.shape[0] >= n and out.shape[1] >= self.nchan
+        if n:
+            call("pdd_psrfits_block", ptr(rows), int(nrows), self.row_bytes, self.data_off,
+                 self.scl_off, self.offs_off, self.wts_off, self.nbits, self.nsblk, self.nchan,
+                 self.npol, self.pol0, self.npol_sum, int(s0), int(n),
+                 _lib.U8 if self.dtype == np.uint8 else _lib.F32, ptr(out), out.stride(0),
+                 stream_ptr(stream))
+        return out[:n, :self.nchan]
+
+
+class PsrfitsSearchFile(object):
+    """A search-mode PSRFITS file as the search tools read a ``filterbank``:
+    ``nchans``, ``freqs`` / ``frequencies`` (DAT_FREQ of row 0, file order),
+    ``tsamp``, ``number_of_samples`` (NAXIS2 * NSBLK), ``nbits``, ``packed``
+    (False), ``dtype`` ("uint8" or "float32": what the device decode emits),
+    ``header`` (tstart, fch1, foff, nchans, tsamp, nbits, ...),
+    ``read_block_into`` and ``close``; plus the row interface of the stream:
+    ``rows_for``, ``read_rows_into`` and ``decoder()``.
+
+    Polarisations (the project's own rule; PRESTO is absent, parity unpinned):
+    NPOL 1 or POL_TYPE AA+BB / INTEN: the one polarisation; AABB / AABBCRCI:
+    AA + BB summed after scales and offsets; IQUV: polarisation 0; ``poln=k``
+    (or the PSRFITS_POLN environment variable): polarisation k alone.
+
+    Mode, decided once over every row of the file: integer (uint8 samples,
+    the file's own values, zeroed where the weight is 0) when nbits is 4 or
+    8, one polarisation is used and every applied DAT_SCL is 1, DAT_OFFS 0
+    and DAT_WTS 0 or 1; float32 ``((v*scl)+offs)*wts`` otherwise.
+    ``apply_*=False`` takes a column out of the test and of the decode."""
+
+    _CHECK_BYTES = 1 << 26  # bound of one slice of the mode scan
+
+    def __init__(self, fn, apply_scales=True, apply_offsets=True, apply_weights=True, poln=None):
+        if not os.path.isfile(fn):
+            raise ValueError("ERROR: File does not exist!\n\t(%s)" % fn)
+        if not is_PSRFITS(fn):
+            raise ValueError("File '%s' is not a search-mode PSRFITS file" % fn)
+        self.filename = fn
+        self.fits = pyfits.open(fn, mode="readonly", memmap=True)
+        primary = self.fits["PRIMARY"].header
+        sub = self.fits["SUBINT"]
+        sh = sub.header
+        names = sub.columns.names
+        self.nbits = int(sh["NBITS"])
+        if self.nbits not in (4, 8, 16, 32):
+            raise ValueError("PSRFITS nbits=%d is not supported (4, 8, 16, 32)" % self.nbits)
+        self.nchans = self.nchan = int(sh["NCHAN"])
+        self.npol = int(sh.get("NPOL", 1))
+        self.pol_type = str(sh.get("POL_TYPE", "AA+BB")).strip()
+        self.nsblk = self.nsamp_per_subint = int(sh["NSBLK"])
+        self.nsubints = int(sh["NAXIS2"])
+        self.number_of_samples = self.nsubints * self.nsblk
+        self.tsamp = float(sh["TBIN"])
+        self.packed = False
+        self.row_bytes = int(sh["NAXIS1"])
+        self._data_offset = int(sub.data_offset)
+        if "DATA" not in names or "DAT_FREQ" not in names:
+            raise ValueError("%s: the SUBINT table has no DATA / DAT_FREQ column" % fn)
+        col = sub.columns[names.index("DATA")]
+        self.data_off = int(col.offset)
+        if col.nbytes * 8 != self.nsblk * self.npol * self.nchans * self.nbits:
+            raise ValueError("%s: DATA holds %d bytes a row, NSBLK x NPOL x NCHAN x NBITS needs %d "
+                             "(a partial last subint is not supported)"
+                             % (fn, col.nbytes, self.nsblk * self.npol * self.nchans * self.nbits // 8))
+        if self.nbits == 4 and (self.npol * self.nchans) % 2:
+            raise ValueError("%s: 4-bit spectra of %d samples do not fill whole bytes"
+                             % (fn, self.npol * self.nchans))
+        # polarisations
+        if poln is None and os.getenv("PSRFITS_POLN") is not None:
+            poln = int(os.getenv("PSRFITS_POLN"))
+        if poln is not None:
+            if not 0 <= int(poln) < self.npol:
+                raise ValueError("polarisation %d of a file with %d" % (poln, self.npol))
+            self.pol0, self.npol_sum = int(poln), 1
+        elif self.npol == 1 or self.pol_type in ("AA+BB", "INTEN", "IQUV"):
+            self.pol0, self.npol_sum = 0, 1
+        elif self.pol_type in ("AABB", "AABBCRCI") and self.npol >= 2:
+            self.pol0, self.npol_sum = 0, 2
+        else:
+            raise ValueError("%s: POL_TYPE %r with NPOL %d: choose a polarisation (poln)"
+                             % (fn, self.pol_type, self.npol))
+        # scale, offset and weight columns in use (-1: not applied)
+        offs = {}
+        for key, want, count in (("DAT_SCL", apply_scales, self.npol * self.nchans),
+                                 ("DAT_OFFS", apply_offsets, self.npol * self.nchans),
+                                 ("DAT_WTS", apply_weights, self.nchans)):
+            offs[key] = -1
+            if want and key in names:
+                c = sub.columns[names.index(key)]
+                if c.code != "E" or c.repeat < count:
+                    raise ValueError("%s: column %s is %s, expected %dE" % (fn, key, c.format, count))
+                offs[key] = int(c.offset)
+        self.scl_off, self.offs_off, self.wts_off = offs["DAT_SCL"], offs["DAT_OFFS"], offs["DAT_WTS"]
+        self.freqs = np.atleast_1d(sub.data[0]["DAT_FREQ"]).astype(np.float64) \
+            if self.nsubints else np.zeros(self.nchans)
+        self.frequencies = self.freqs
+        self.is_hifreq_first = bool(len(self.freqs) > 1 and self.freqs[1] < self.freqs[0])
+        self.dtype = "uint8" if self._integer_mode() else "float32"
+        if self.dtype == "uint8":
+            self.scl_off = self.offs_off = -1  # all 1 and 0: the file's own values
+        tstart = (primary.get("STT_IMJD", 0) + (primary.get("STT_SMJD", 0) +
+                                                primary.get("STT_OFFS", 0.0)) / SECPERDAY
+                  + self.tsamp * self.nsblk * sh.get("NSUBOFFS", 0) / SECPERDAY)
+        foff = float(self.freqs[1] - self.freqs[0]) if self.nchans > 1 else \
+            float(sh.get("CHAN_BW", 1.0))
+        self.header = {"tstart": float(tstart), "fch1": float(self.freqs[0]), "foff": foff,
+                       "nchans": self.nchans, "tsamp": self.tsamp, "nbits": self.nbits,
+                       "nifs": 1, "source_name": str(primary.get("SRC_NAME", "")),
+                       "telescope": str(primary.get("TELESCOP", ""))}
+        self._f = open(fn, "rb")
+
+    def _integer_mode(self):
+        """The mode decision over every row, read through the memmap in
+        bounded slices."""
+        if self.nbits not in (4, 8) or self.npol_sum != 1:
+            return False
+        data = self.fits["SUBINT"].data
+        lo_c, hi_c = self.pol0 * self.nchans, (self.pol0 + 1) * self.nchans
+        step = max(1, self._CHECK_BYTES // max(1, 12 * self.nchans))
+        for r0 in range(0, self.nsubints, step):
+            part = data[r0:r0 + step]
+            if self.scl_off >= 0 and np.any(np.asarray(part["DAT_SCL"]).reshape(
+                    len(part), -1)[:, lo_c:hi_c] != 1):
+                return False
+            if self.offs_off >= 0 and np.any(np.asarray(part["DAT_OFFS"]).reshape(
+                    len(part), -1)[:, lo_c:hi_c] != 0):
+                return False
+            if self.wts_off >= 0:
+                w = np.asarray(part["DAT_WTS"]).reshape(len(part), -1)[:, :self.nchans]
+                if np.any((w != 0) & (w != 1)):
+                    return False
+        return True
+
+    def close(self):
+        f = self.__dict__.get("_f")
+        if f is not None and not f.closed:
+            f.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decoder(self):
+        return PsrfitsDecoder(self.row_bytes, self.data_off, self.scl_off, self.offs_off,
+                              self.wts_off, self.nbits, self.nsblk, self.nchans, self.npol,
+                              self.pol0, self.npol_sum, self.nsubints, self.dtype)
+
+    def rows_for(self, start, n):
+        """(row0, nrows, s0): the rows that hold samples [start, start + n)
+        and the offset of ``start`` in the first of them.  A row on a seam of
+        two spans belongs to both."""
+        return self.decoder().rows_for(start, n)
+
+    def read_rows_into(self, row0, out):
+        """Rows row0 ... as stored into ``out``, a C-contiguous uint8
+        [k, NAXIS1] host array (numpy, or a pinned tensor's .numpy()), in one
+        contiguous read; returns the number of whole rows read (fewer at the
+        end of the table).  Refusals as filterbank.read_block_into."""
+        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("read_rows_into: out must be a C-contiguous numpy array")
+        if out.ndim != 2 or out.shape[1] != self.row_bytes or out.dtype != np.uint8:
+            raise ValueError("read_rows_into: out must be [k, %d] of uint8, not %s of %s"
+                             % (self.row_bytes, out.shape, out.dtype))
+        k = max(0, min(out.shape[0], self.nsubints - int(row0)))
+        if k == 0:
+            return 0
+        self._f.seek(self._data_offset + int(row0) * self.row_bytes)
+        got = self._f.readinto(memoryview(out.reshape(-1))[:k * self.row_bytes])
+        return got // self.row_bytes
+
+    def read_device(self, start, n, out=None, piece_bytes=1 << 28):
+        """Samples [start, start + n) decoded on the device into ``out``
+        (device [>= n, nchans] of ``dtype``; made here when None): the rows go
+        up and are decoded in pieces of at most ``piece_bytes``.  Returns
+        out[:n read]."""
+        import torch
+        from .. import _lib
+        _lib.require_gpu()
+        dec = self.decoder()
+        n = max(0, min(int(n), self.number_of_samples - int(start)))
+        if out is None:
+            out = torch.empty((n, self.nchans), dtype=dec.torch_dtype, device="cuda")
+        per = max(1, piece_bytes // self.row_bytes) * self.nsblk  # samples a piece
+        host = None
+        done = 0
+        while done < n:
+            m = min(per, n - done)
+            row0, nrows, s0 = dec.rows_for(start + done, m)
+            if host is None:
+                host = np.empty((dec.max_rows(min(per, n)), self.row_bytes), dtype=np.uint8)
+            got = self.read_rows_into(row0, host[:nrows])
+            if got != nrows:
+                raise IOError("%s: short read, %d of %d rows" % (self.filename, got, nrows))
+            dec.decode(torch.from_numpy(host[:nrows]).cuda(), nrows, s0, m, out[done:done + m])
+            done += m
+        return out[:n]
+
+    def read_block_into(self, startsamp, out):
+        """Samples [startsamp, startsamp + len(out)) into ``out``, a
+        C-contiguous host array [n, nchans] of ``dtype``; returns the number
+        of spectra read (fewer at the end of the file).  Goes through the
+        device (rows up, pdd_psrfits_block, block back): for windows -- the
+        mask's fill, cut-outs, subband folds -- not for the stream."""
+        import torch
+        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("read_block_into: out must be a C-contiguous numpy array")
+        if out.ndim != 2 or out.shape[1] != self.nchans or out.dtype != self.dtype:
+            raise ValueError("read_block_into: out must be [n, %d] of %s, not %s of %s"
+                             % (self.nchans, self.dtype, out.shape, out.dtype))
+        n = max(0, min(out.shape[0], self.number_of_samples - int(startsamp)))
+        if n:
+            torch.from_numpy(out[:n]).copy_(self.read_device(int(startsamp), n))
+        return n
+
+
+def open_search_file(fn, **kw):
+    """The input of a search: a ``filterbank`` (SIGPROC) or a
+    ``PsrfitsSearchFile``, decided by content (a FITS file starts with
+    ``SIMPLE  =``), not by extension.  ``kw``: PsrfitsSearchFile's options
+    (apply_scales, apply_offsets, apply_weights, poln), noted and ignored for
+    a filterbank.  A FITS file that is not search-mode PSRFITS is refused."""
+    if not os.path.isfile(fn):
+        raise ValueError("ERROR: File does not exist!\n\t(%s)" % fn)
+    with open(fn, "rb") as f:
+        magic = f.read(9)
+    if magic == b"SIMPLE  =":
+        if not is_PSRFITS(fn):
+            raise ValueError("%s is a FITS file but not a search-mode PSRFITS file "
+                             "(FITSTYPE 'PSRFITS', OBS_MODE 'SEARCH')" % fn)
+        return PsrfitsSearchFile(fn, **kw)
+    from .filterbank import filterbank
+    if any(kw.get(k) is False for k in ("apply_scales", "apply_offsets", "apply_weights")) \
+            or kw.get("poln") is not None:
+        print("%s is a SIGPROC filterbank: the PSRFITS scale, offset, weight and polarisation "
+              "options are ignored" % fn)
+    return filterbank(fn)
+
+
 def write_search_psrfits(fn, data, freqs, tbin, nbits, scales=None, offsets=None, weights=None,
-                         primary=None, nsuboffs=0):
-    """Write a single-polarisation search-mode PSRFITS file (test fixtures and
-    mock data).  ``data``: [nsub, nsblk, nchan] samples in FILE channel order
+                         primary=None, nsuboffs=0, npol=1, pol_type="AA+BB"):
+    """Write a search-mode PSRFITS file (test fixtures and mock data).
+    ``data``: [nsub, nsblk, nchan] samples in FILE channel order
     (uint8 0..15 for nbits 4 -- packed low nibble first, uint8 for 8, int16
     for 16, float32 for 32); ``freqs``: the DAT_FREQ column (either order);
-    scales/offsets/weights: [nsub, nchan] (defaults 1, 0, 1)."""
+    scales/offsets/weights: [nsub, nchan] (defaults 1, 0, 1).  With
+    ``npol`` > 1 (``pol_type`` e.g. "AABB", "IQUV") ``data`` is
+    [nsub, nsblk, npol, nchan] and scales and offsets are [nsub, npol*nchan]."""
     data = np.asarray(data)
-    nsub, nsblk, nchan = data.shape
+    if npol == 1:
+        nsub, nsblk, nchan = data.shape
+    else:
+        nsub, nsblk, dpol, nchan = data.shape
+        if dpol != npol:
+            raise ValueError("data holds %d polarisations, npol is %d" % (dpol, npol))
+    nper = nsblk * npol * nchan
     if nbits == 4:
         flat = data.reshape(nsub, -1).astype(np.uint8)
         body = (flat[:, 0::2] & 15) | ((flat[:, 1::2] & 15) << 4)
         tform = "%dB" % body.shape[1]
     elif nbits == 8:
-        body, tform = data.reshape(nsub, -1).astype(np.uint8), "%dB" % (nsblk * nchan)
+        body, tform = data.reshape(nsub, -1).astype(np.uint8), "%dB" % nper
     elif nbits == 16:
-        body, tform = data.reshape(nsub, -1).astype(">i2"), "%dI" % (nsblk * nchan)
+        body, tform = data.reshape(nsub, -1).astype(">i2"), "%dI" % nper
     elif nbits == 32:
-        body, tform = data.reshape(nsub, -1).astype(">f4"), "%dE" % (nsblk * nchan)
+        body, tform = data.reshape(nsub, -1).astype(">f4"), "%dE" % nper
     else:
         raise ValueError("nbits must be 4, 8, 16 or 32")
     ones = np.ones((nsub, nchan), dtype=np.float32)
-    scales = ones if scales is None else np.asarray(scales, dtype=np.float32)
-    offsets = 0 * ones if offsets is None else np.asarray(offsets, dtype=np.float32)
+    pones = np.ones((nsub, npol * nchan), dtype=np.float32)
+    scales = pones if scales is None else np.asarray(scales, dtype=np.float32)
+    offsets = 0 * pones if offsets is None else np.asarray(offsets, dtype=np.float32)
     weights = ones if weights is None else np.asarray(weights, dtype=np.float32)
     freqs = np.asarray(freqs, dtype=np.float64)
     cols = [("TSUBINT", "1D"), ("OFFS_SUB", "1D"), ("TEL_AZ", "1E"), ("TEL_ZEN", "1E"),
-            ("DAT_FREQ", "%dD" % nchan), ("DAT_WTS", "%dE" % nchan), ("DAT_OFFS", "%dE" % nchan),
-            ("DAT_SCL", "%dE" % nchan), ("DATA", tform)]
+            ("DAT_FREQ", "%dD" % nchan), ("DAT_WTS", "%dE" % nchan),
+            ("DAT_OFFS", "%dE" % (npol * nchan)), ("DAT_SCL", "%dE" % (npol * nchan)),
+            ("DATA", tform)]
     rows = {
         "TSUBINT": np.full(nsub, nsblk * tbin), "OFFS_SUB": (np.arange(nsub) + 0.5) * nsblk * tbin,
         "TEL_AZ": np.full(nsub, 123.5, dtype=np.float32),
@@ -506,6 +809,6 @@ def write_search_psrfits(fn, data, freqs, tbin, nbits, scales=None, offsets=None
         d = dict(p)
         d.update(primary)
         p = list(d.items())
-    sub = [("TBIN", float(tbin)), ("NCHAN", nchan), ("NPOL", 1), ("POL_TYPE", "AA+BB"),
+    sub = [("TBIN", float(tbin)), ("NCHAN", nchan), ("NPOL", npol), ("POL_TYPE", pol_type),
            ("NCHNOFFS", 0), ("NSBLK", nsblk), ("NBITS", nbits), ("NSUBOFFS", nsuboffs)]
     pyfits.write(fn, p, [("SUBINT", sub, cols, rows)])

@@ -132,7 +132,7 @@ class StreamingSearch(object):
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm=True, dtype=None,
                  threshold=6.0, widths=DEFAULT_WIDTHS, detrendlen=1024, max_cands=1 << 20,
-                 rfimask=None, nbits=8):
+                 rfimask=None, nbits=8, decoder=None):
         from .stream import StreamingSweep
         kw = {} if dtype is None else {"dtype": dtype}
         if rfimask is not None:
@@ -140,6 +140,9 @@ class StreamingSearch(object):
         if nbits != 8:
             # chunks are packed rows, uint8 [n, C*nbits/8] (StreamingSweep)
             kw["nbits"] = nbits
+        if decoder is not None:
+            # chunks are SUBINT rows of a PSRFITS file, decoded on the device
+            kw["decoder"] = decoder
         self.sweep = StreamingSweep(dms, freqs, dt, block=block, downsamp=downsamp,
                                     zero_dm=zero_dm, **kw)
         self.search = SinglePulseSearch(threshold, widths, detrendlen, max_cands)

@@ -27,6 +27,14 @@ included; otherwise the block is unpacked (pdd_unpack_bits) into an 8-bit
 block that takes the 8-bit path.  ``"auto"`` is then ``"int"`` where its bound
 fits, else ``"float"`` (a uint8 wrap of 2-bit values is noise).
 
+PSRFITS input (``decoder``: a formats.psrfits.PsrfitsDecoder): chunks are the
+file's own SUBINT rows, uint8 [k, row_bytes] -- the rows of the block's
+samples, a seam row in both chunks -- copied into rotating device row
+buffers and decoded there (pdd_psrfits_block) into one raw block of the
+decoder's type, 8-bit or float32, which takes the paths above; the overlap is
+decoded from the next chunk's rows straight to the block's tail
+(``StreamingSweep._call_rows``).
+
 Per input chunk (``block`` spectra of the stream, time-major [n, nchan] in
 file order, 8/16-bit or float32):
 
@@ -104,8 +112,16 @@ class StreamingSweep(object):
     (downsampled time index)."""
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm="auto",
-                 dtype=torch.uint8, device="cuda", rfimask=None, nbits=8):
+                 dtype=torch.uint8, device="cuda", rfimask=None, nbits=8, decoder=None):
         _lib.require_gpu()
+        # decoder: a formats.psrfits.PsrfitsDecoder -- chunks are the file's
+        # own SUBINT rows (pinned uint8 [k, row_bytes]), decoded on the device
+        # into the raw block of the decoder's dtype (see __call__)
+        self.decoder = decoder
+        if decoder is not None:
+            assert nbits == 8, "a decoder emits 8-bit or float32 blocks"
+            assert decoder.nchan == len(freqs), "the decoder's channels are not the stream's"
+            dtype = decoder.torch_dtype
         # nbits 1, 2 or 4: chunks are packed rows, host uint8 [n, C*nbits/8]
         # (SIGPROC bit order), unpacked on the device
         if nbits not in (1, 2, 4, 8):
@@ -193,8 +209,15 @@ class StreamingSweep(object):
         assert self.ov <= self.block, "block must hold the overlap (max delay x downsamp)"
         n_raw = self.block + self.ov
         self.nbuf = 3
+        # with a decoder the row buffers rotate and one raw block suffices: it
+        # is written (decode) and read (prologue) on the compute stream alone
         self.raw = [torch.empty((n_raw, self.row_bytes), dtype=dtype, device=self.device)
-                    for _ in range(self.nbuf)]
+                    for _ in range(self.nbuf if decoder is None else 1)]
+        self.rows = None
+        if decoder is not None:
+            self.rows = [torch.empty((decoder.max_rows(self.block), decoder.row_bytes),
+                                     dtype=torch.uint8, device=self.device)
+                         for _ in range(self.nbuf)]
         # the 8-bit block of a packed stream off the fused path
         self.unpacked = (torch.empty((n_raw, self.C), dtype=torch.uint8, device=self.device)
                          if self.packed and not self.fused else None)
@@ -244,6 +267,10 @@ class StreamingSweep(object):
         and the head of the next one, so a run resumed at block k -- chunks
         k, k+1, ... of the stream and ``start_block=k`` -- yields exactly the
         (t0, plane) pairs of blocks k, k+1, ... of the uninterrupted run."""
+        if self.decoder is not None:
+            for item in self._call_rows(chunks, planes, start_block):
+                yield item
+            return
         cur = torch.cuda.current_stream(self.device)
         prev = None  # (buffer index, n spectra)
         t0 = int(start_block) * self.n_out_block
@@ -283,6 +310,72 @@ class StreamingSweep(object):
             cur.wait_event(self.h2d[pb])
             out = None if planes is None else planes[emitted % len(planes)]
             plane = self._process(self.raw[pb], pn, out, s0)
+            self.free[pb].record(cur)
+            yield t0, plane
+
+    def _call_rows(self, chunks, planes, start_block):
+        """__call__ with a decoder.  Chunk i (counted from ``start_block``) is
+        a host uint8 [k, row_bytes] tensor (pinned for an asynchronous copy)
+        holding the SUBINT rows of samples [i block, (i+1) block) as
+        ``decoder.rows_for`` names them; a row on a block seam is in both
+        chunks.
+
+            copy stream : chunk i's rows holding its first ov samples
+                              --H2D--> rows[i % 3]             (head, event)
+                          its other rows --H2D--> rows[i % 3]  (rest, event)
+            compute     : decode(rows[(i-1) % 3]) -> raw[0 : block]
+                          decode(rows[i % 3], first ov samples) -> raw[block : block + ov]
+                          [mask], prologue, sweep as without a decoder
+
+        The decode addresses any sample range of the rows, so the overlap is
+        decoded where it is needed (no D2D append); ``free[b]`` guards the row
+        buffer."""
+        dec = self.decoder
+        cur = torch.cuda.current_stream(self.device)
+        raw = self.raw[0]
+        prev = None  # (buffer index, n spectra, rows, offset of the first sample)
+        t0 = int(start_block) * self.n_out_block
+        s0 = int(start_block) * self.block
+        emitted = 0
+        for i, chunk in enumerate(chunks):
+            b = i % self.nbuf
+            start = (int(start_block) + i) * self.block
+            row0, nrows, off = dec.rows_for(start, self.block)
+            n = min(self.block, dec.number_of_samples - start)
+            assert n > 0 and tuple(chunk.shape) == (nrows, dec.row_bytes), \
+                "chunk %d must hold the %d rows of its samples" % (i, nrows)
+            head = min(self.ov, n)
+            nh = (off + head - 1) // dec.nsblk + 1 if head else 0  # rows of the head
+            self.copy_stream.wait_event(self.free[b])
+            with torch.cuda.stream(self.copy_stream):
+                if nh:
+                    self.rows[b][:nh].copy_(chunk[:nh], non_blocking=True)
+                self.h2d_head[b].record(self.copy_stream)
+                if nrows > nh:
+                    self.rows[b][nh:nrows].copy_(chunk[nh:], non_blocking=True)
+            self.h2d[b].record(self.copy_stream)
+            if prev is not None:
+                pb, pn, pr, poff = prev
+                assert pn == self.block, "only the last chunk may be short"
+                cur.wait_event(self.h2d[pb])
+                cur.wait_event(self.h2d_head[b])
+                dec.decode(self.rows[pb], pr, poff, pn, raw)
+                if head:
+                    dec.decode(self.rows[b], nh, off, head, raw[pn:])
+                out = None if planes is None else planes[emitted % len(planes)]
+                emitted += 1
+                plane = self._process(raw, pn + head, out, s0)
+                self.free[pb].record(cur)
+                yield t0, plane
+                t0 += plane.shape[1]
+                s0 += pn
+            prev = (b, n, nrows, off)
+        if prev is not None:
+            pb, pn, pr, poff = prev
+            cur.wait_event(self.h2d[pb])
+            dec.decode(self.rows[pb], pr, poff, pn, raw)
+            out = None if planes is None else planes[emitted % len(planes)]
+            plane = self._process(raw, pn, out, s0)
             self.free[pb].record(cur)
             yield t0, plane
 
