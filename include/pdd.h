@@ -542,6 +542,30 @@ int pdd_acc_search(const float* powers, int64_t D, int nz, int64_t ni, const int
                    int n_harms, const float* thr, int64_t rlo, int32_t* cands, int64_t max_cands,
                    unsigned long long* count, void* stream);
 
+/* ---- jerk search (pypulsar_amd/jerk.py; restated in tests/jerk_oracle.py).
+ * vol: [nw][D][nz][ni] float32, contiguous: slab l = the powers
+ * pdd_acc_correlate writes for all D rows with the taps of the jerk w_l = (l -
+ * L0) dw (L0 = (nw - 1) / 2, lc = l - L0; J0, jc as above). */
+/* Harmonic stages on the TOP harmonic's grid -- pdd_acc_search's rule in both
+ * template axes -- and the candidate search of the volume.  harms, thr: HOST
+ * arrays as for pdd_acc_search.
+ *   S_H[lc][jc][i] = sum_{h=1..H} P[L0 + floor((lc h + H / 2) / H)][d]
+ *                                  [J0 + floor((jc h + H / 2) / H)][(i h + H / 2) / H]
+ * (float32, ascending h from the h = 1 term).  Cell (l, j, i) with i >= 2 H
+ * rlo is a candidate of stage H when S >= thr, S > each of the 13 of its 26
+ * neighbours that precede it in (l, j, i) order and S >= each of the 13 that
+ * follow; neighbours outside [0, nw) x [0, nz) x [2 H rlo, ni) count as -inf
+ * (nw = 1: pdd_acc_search's rule).  scratch: DEVICE, scratch_floats >= 3 D nz
+ * ni floats (a ring of three S_H slabs; contents undefined afterwards).  nw
+ * odd, <= 63; nz odd, <= 255.  Records int32[8] {row, i, jc, lc, H, float-bits
+ * S, 0, 0} are appended through the device counter *count exactly as by
+ * pdd_acc_search (always incremented, stored while < max_cands: the caller
+ * checks for overflow). */
+int pdd_jerk_search(const float* vol, int64_t D, int nw, int nz, int64_t ni, const int32_t* harms,
+                    int n_harms, const float* thr, int64_t rlo, float* scratch,
+                    int64_t scratch_floats, int32_t* cands, int64_t max_cands,
+                    unsigned long long* count, void* stream);
+
 /* ---- Fourier-domain interference zapping (pypulsar_amd/zap.py; restated in
  * tests/zap_oracle.py).  powers: whitened powers of pdd_ps_normalise, one
  * spectrum a row. */

@@ -57,7 +57,7 @@ EXPORTS = (
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
     "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm", "pdd_unpack_bits",
-    "pdd_zdm_packed_int_downsample", "pdd_psrfits_block",
+    "pdd_zdm_packed_int_downsample", "pdd_psrfits_block", "pdd_jerk_search",
 )
 
 
@@ -148,6 +148,8 @@ _SIGS = {
                          _vp], _int),
     "pdd_acc_correlate": ([_vp, _i64, _i64, _i64, _vp, _vp, _int, _int, _vp, _vp], _int),
     "pdd_acc_search": ([_vp, _i64, _int, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp], _int),
+    "pdd_jerk_search": ([_vp, _i64, _int, _int, _i64, _vp, _int, _vp, _i64, _vp, _i64, _vp, _i64,
+                         _vp, _vp], _int),
     "pdd_rfi_stats_prep": ([_vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
                            _int),
     "pdd_rfi_stats_power": ([_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp], _int),

@@ -23,6 +23,12 @@ holds the phase-versus-frequency image.  With ``--zmax Z`` the
 rows are searched for signals that drift up to Z Fourier bins over the
 observation (pulsars in binaries; pypulsar_amd.accel): the candidates carry
 their ``z``, and a fold starts from their frequency derivative.  With
+``--wmax W`` the templates also carry a jerk of up to W bins (``w = fdd T^3``:
+tight binaries in long observations; pypulsar_amd.jerk): the ``.accelcands``
+names end in ``_JERK_<W>``, ``<base>_jerkcands.npz`` holds every sifted
+candidate's ``w`` and second derivative (the ``.accelcands`` layout has no
+column for them), and a fold starts from the frequency and its derivative at
+the first sample.  With
 ``--ffa`` the plane is also searched by fast folding (pypulsar_amd.ffa: slow,
 narrow pulses that the harmonic sums lose); its sifted candidates go to
 ``<base>.ffacands`` in the same layout, and ``--fold K`` folds its K strongest
@@ -43,6 +49,7 @@ periodicity or acceleration search.
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 --fold-subbands 32 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 --wmax 100 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --autozap obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zaplist site.zaplist obs.fil
@@ -60,12 +67,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
                 nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2, maskfile=None,
-                rfifind=None, zaplist=None, autozap=None, file_kw=None):
+                rfifind=None, zaplist=None, autozap=None, file_kw=None, wmax=0, dw=20,
+                jerk_workspace_bytes=None):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
     pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
     acceleration search (pypulsar_amd.accel.AccelSearch, records of
     ACCEL_CAND_DTYPE) on a z grid of ``dz``; ``harms`` then at most 16.
+    ``wmax`` > 0: the jerk search (pypulsar_amd.jerk.JerkSearch, records of
+    JERK_CAND_DTYPE) on that z grid (``zmax`` may be 0) and a w grid of ``dw``,
+    its row batches bounded by ``jerk_workspace_bytes`` (None: its default).
     ``maskfile`` / ``rfifind``: the cells of that rfifind ``.mask``, or of the
     one made here from the data with intervals of ``rfifind`` seconds (left as
     <base>_rfifind.mask), are replaced by their channel's level first.
@@ -119,7 +130,11 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     sw = DMSweep(dms, fb.freqs, dt, dtype="f32")
     plane = sw(img, trim=True)
     del img
-    if zmax > 0:
+    if wmax > 0:
+        from pypulsar_amd.jerk import DEFAULT_HARMS as JERK_HARMS, JerkSearch
+        jkw = {} if jerk_workspace_bytes is None else {"workspace_bytes": jerk_workspace_bytes}
+        ps = JerkSearch(sigma, zmax, wmax, dz, dw, harms or JERK_HARMS, flo=flo, **jkw)
+    elif zmax > 0:
         from pypulsar_amd.accel import DEFAULT_HARMS as ACCEL_HARMS, AccelSearch
         ps = AccelSearch(sigma, zmax, dz, harms or ACCEL_HARMS, flo=flo)
     else:
@@ -133,7 +148,7 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
         if autozap is not None:
             finder = autozap if isinstance(autozap, _zap.BirdieFinder) else _zap.BirdieFinder()
             nf = PeriodicitySearch.default_nfft(plane.shape[1]) if nfft is None else int(nfft)
-            found = finder.find(ps.ps if zmax > 0 else ps, plane, dt, nfft=nf)
+            found = finder.find(ps.ps if zmax > 0 or wmax > 0 else ps, plane, dt, nfft=nf)
             out = os.path.splitext(infile)[0] + ".zaplist"
             _zap.write_zaplist(out, found)
             b = found.bins(nf, dt)
@@ -199,6 +214,17 @@ def main(argv=None):
                            "(Default: 0, the periodicity search)")
     parser.add_option("--dz", type="int", default=2,
                       help="Step of the z grid of the acceleration search. (Default: 2)")
+    parser.add_option("--wmax", type="int", default=0,
+                      help="Largest searched jerk in Fourier bins over the observation "
+                           "(w = fdd T^3): the jerk search, on the z grid of --zmax (which may "
+                           "be 0); caps --numharm at 16; also writes <base>_jerkcands.npz. "
+                           "(Default: 0, no jerk)")
+    parser.add_option("--dw", type="int", default=20,
+                      help="Step of the w grid of the jerk search. (Default: 20)")
+    parser.add_option("--jerk-workspace-gib", dest="jerk_workspace_gib", type="float",
+                      default=None, metavar="G",
+                      help="Device memory in GiB that bounds a row batch of the jerk search, "
+                           "whose whole volume of a row must be resident. (Default: 32)")
     parser.add_option("--fold", type="int", default=0,
                       help="Fold the K strongest sifted candidates on the plane and refine "
                            "period, period derivative and DM; writes <base>_cand<k>.bestprof "
@@ -257,9 +283,12 @@ def main(argv=None):
     from pypulsar_amd.periodicity import sift, write_accelcands
     if options.zmax < 0 or options.dz < 1:
         parser.error("--zmax must be >= 0 and --dz >= 1")
+    if options.wmax < 0 or options.dw < 1:
+        parser.error("--wmax must be >= 0 and --dw >= 1")
+    accelerated = options.zmax > 0 or options.wmax > 0
     if options.fold_subbands < 0 or (options.fold_subbands and options.fold <= 0):
         parser.error("--fold-subbands NSUB needs NSUB >= 0 and --fold K")
-    numharm = min(options.numharm, 16) if options.zmax > 0 else options.numharm
+    numharm = min(options.numharm, 16) if accelerated else options.numharm
     harms = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= numharm) or (1,)
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
     finder = None
@@ -274,15 +303,26 @@ def main(argv=None):
                       return_plane=options.fold > 0 or options.ffa, zmax=options.zmax,
                       dz=options.dz,
                       maskfile=options.maskfile, rfifind=options.rfifind,
-                      zaplist=options.zaplist, autozap=finder, file_kw=options.file_kw)
+                      zaplist=options.zaplist, autozap=finder, file_kw=options.file_kw,
+                      wmax=options.wmax, dw=options.dw,
+                      jerk_workspace_bytes=None if options.jerk_workspace_gib is None
+                      else int(options.jerk_workspace_gib * (1 << 30)))
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]
     out = options.outname or base + ".accelcands"
-    write_accelcands(sifted, out, basename=os.path.basename(base), zmax=options.zmax)
+    write_accelcands(sifted, out, basename=os.path.basename(base), zmax=options.zmax,
+                     wmax=options.wmax)
     print("%d candidates (%d sifted) -> %s" % (len(cands), len(sifted), out))
+    to_fold = sifted[:options.fold]
+    if options.wmax > 0:
+        jout = os.path.splitext(out)[0] + "_jerkcands.npz"
+        write_jerkcands(sifted, jout)
+        print("w and the second derivative of the %d sifted candidates -> %s" % (len(sifted), jout))
+        if options.fold > 0:
+            to_fold = first_sample_starts(to_fold, res[2].shape[1] * res[1])
     if options.fold > 0:
-        folded = fold_candidates(res[2], dms, res[1], sifted[:options.fold],
+        folded = fold_candidates(res[2], dms, res[1], to_fold,
                                  os.path.splitext(out)[0], args[0], options.fold_npart,
                                  options.fold_nbins, options.fold_dm_halfwidth)
         if options.fold_subbands:
@@ -304,6 +344,41 @@ def main(argv=None):
             if options.fold_subbands:
                 fold_subbands(folded, os.path.splitext(out)[0], args[0], options, tag="ffacand")
     return 0
+
+
+def write_jerkcands(sifted, fn):
+    """``<base>_jerkcands.npz``: per sifted candidate of the jerk search, by
+    descending sigma (the order of the ``.accelcands`` file), ``DM``, ``r``,
+    ``period`` (s, mid-observation), ``numharm``, ``sigma``, ``z`` and ``w``
+    (bins of 1/T), ``fd`` (Hz / s, the mean) and ``fdd`` (Hz / s^2), ``accel``
+    (m / s^2) and ``jerk`` (m / s^3)."""
+    from pypulsar_amd.accel import C_LIGHT
+    cl = sorted(sifted, key=lambda c: -c.sigma)
+    col = lambda f, t="f8": np.asarray([f(c) for c in cl], dtype=t)  # noqa: E731
+    np.savez(fn, DM=col(lambda c: c.dm), r=col(lambda c: c.r), period=col(lambda c: c.period),
+             numharm=col(lambda c: c.numharm, "i4"), sigma=col(lambda c: c.sigma),
+             z=col(lambda c: c.z), w=col(lambda c: c.w), fd=col(lambda c: c.fd),
+             fdd=col(lambda c: c.fdd), accel=col(lambda c: c.fd * C_LIGHT * c.period),
+             jerk=col(lambda c: c.fdd * C_LIGHT * c.period))
+
+
+def first_sample_starts(sifted, T):
+    """Copies of candidates of the jerk search for pypulsar_amd.fold, which
+    has no second derivative: their ``fd`` becomes the derivative at the first
+    sample, ``fd - fdd T / 2``, and their frequency is set so that the fold
+    starts at the first sample's, ``f - fd T / 2 + fdd T^2 / 12`` (``f``,
+    ``fd``: the means over the ``T`` seconds)."""
+    import copy
+    out = []
+    for c in sifted:
+        f0 = c.freq - 0.5 * c.fd * T + c.fdd * T * T / 12.0
+        fd0 = c.fd - 0.5 * c.fdd * T
+        s = copy.copy(c)
+        s.fd = fd0
+        # (Folder starts a candidate with fd != 0 at freq - fd T / 2)
+        s.period = 1.0 / (f0 + 0.5 * fd0 * T if fd0 != 0.0 else f0)
+        out.append(s)
+    return out
 
 
 def fold_subbands(folded, base, infile, options, tag="cand"):

@@ -355,12 +355,16 @@ class SiftedCandidate(object):
     ``z``: the drift in Fourier bins over the observation and ``fd`` the
     frequency derivative (Hz / s) of a candidate of the acceleration search
     (pypulsar_amd.accel), whose ``period`` is the mid-observation one; both 0
-    otherwise."""
+    otherwise.  ``w``: the jerk in Fourier bins over the observation and
+    ``fdd`` the frequency's second derivative (Hz / s^2) of a candidate of the
+    jerk search (pypulsar_amd.jerk), whose ``z`` and ``fd`` are the means over
+    the observation; both 0 otherwise."""
 
     def __init__(self, dm, r, period, numharm, power, sigma, row=-1, accelfile=None, candnum=None,
-                 z=0.0, fd=0.0):
+                 z=0.0, fd=0.0, w=0.0, fdd=0.0):
         self.dm, self.r, self.period = float(dm), float(r), float(period)
         self.z, self.fd = float(z), float(fd)
+        self.w, self.fdd = float(w), float(fdd)
         self.numharm, self.power, self.sigma = int(numharm), float(power), float(sigma)
         self.row = int(row)
         self.accelfile, self.candnum = accelfile, candnum
@@ -384,12 +388,16 @@ def sift(cands, rtol_bins=1.5, max_ratio=16):
     each DM keeps its best sigma.  Records of the acceleration search (with a
     ``zbins`` field, the drift in bins of ``r``) match within ``rtol_bins +
     0.5 |zbins_a - m zbins_b|``: the Fresnel sidelobes of one signal lie
-    within half the z difference in r.  Returns SiftedCandidates by
-    descending sigma."""
+    within half the z difference in r.  Records of the jerk search (with a
+    ``wbins`` field, the jerk in bins of ``r``) widen that by ``|wbins_a - m
+    wbins_b| / 12``: the instantaneous frequency of a signal leaves its mean
+    by at most a twelfth of its jerk (reasoned the same way, not measured).
+    Returns SiftedCandidates by descending sigma."""
     order = np.argsort(-cands["sigma"], kind="stable")
     kept, kept_r = [], np.empty(0)
     has_z = cands.dtype.names is not None and "zbins" in cands.dtype.names
-    kept_z = np.empty(0)
+    has_w = cands.dtype.names is not None and "wbins" in cands.dtype.names
+    kept_z, kept_w = np.empty(0), np.empty(0)
     m = np.arange(1, int(max_ratio) + 1, dtype=np.float64)
     for i in order:
         c = cands[i]
@@ -402,6 +410,10 @@ def sift(cands, rtol_bins=1.5, max_ratio=16):
                 zb = float(c["zbins"])
                 zbig, zsmall = np.where(kept_r >= r, kept_z, zb), np.where(kept_r >= r, zb, kept_z)
                 tol = rtol_bins + 0.5 * np.abs(zbig[:, None] - m[None, :] * zsmall[:, None])
+            if has_w:
+                wb = float(c["wbins"])
+                wbig, wsmall = np.where(kept_r >= r, kept_w, wb), np.where(kept_r >= r, wb, kept_w)
+                tol = tol + np.abs(wbig[:, None] - m[None, :] * wsmall[:, None]) / 12.0
             rel = np.any(np.abs(big[:, None] - m[None, :] * small[:, None]) <= tol, axis=1)
             hit = np.flatnonzero(rel)
             if len(hit):
@@ -412,6 +424,9 @@ def sift(cands, rtol_bins=1.5, max_ratio=16):
             if has_z:
                 s.z, s.fd = float(c["z"]), float(c["fd"])
                 kept_z = np.append(kept_z, float(c["zbins"]))
+            if has_w:
+                s.w, s.fdd = float(c["w"]), float(c["fdd"])
+                kept_w = np.append(kept_w, float(c["wbins"]))
             s._hits = {float(c["DM"]): float(c["sigma"])}
             kept.append(s)
             kept_r = np.append(kept_r, r)
@@ -430,7 +445,7 @@ ACCELCANDS_HEADER = ("#" + "file:candnum".center(66) + "DM".center(9) + "SNR".ce
                      "numhits".center(9) + "\n")
 
 
-def write_accelcands(sifted, fn, basename="pulsar_search", zmax=0):
+def write_accelcands(sifted, fn, basename="pulsar_search", zmax=0, wmax=0):
     """Write SiftedCandidates in the ``.accelcands`` layout of
     formats/accelcands.py (``Candidate.__str__`` / ``DMHit.__str__``), by
     descending sigma, hits by ascending DM.  This search has no coherent
@@ -438,13 +453,15 @@ def write_accelcands(sifted, fn, basename="pulsar_search", zmax=0):
     the sigma (also for the hits); ``z`` is the candidate's (0 unless it comes
     from the acceleration search).  Candidates without a name are called
     ``<basename>_DM<dm>_ACCEL_<zmax>:<n>`` (``zmax``: the searched range, 0
-    for the periodicity search)."""
+    for the periodicity search), with ``_JERK_<wmax>`` appended when ``wmax``
+    > 0 (the jerk search; the layout has no column for ``w``)."""
+    jerk = "_JERK_%d" % int(wmax) if int(wmax) > 0 else ""
     cl = sorted(sifted, key=lambda c: -c.sigma)
     with open(fn, "w") as f:
         f.write(ACCELCANDS_HEADER)
         for n, c in enumerate(cl):
             name = c.accelfile if c.accelfile is not None \
-                else "%s_DM%.2f_ACCEL_%d" % (basename, c.dm, int(zmax))
+                else "%s_DM%.2f_ACCEL_%d%s" % (basename, c.dm, int(zmax), jerk)
             cand = "%s:%d" % (name, c.candnum if c.candnum is not None else n + 1)
             f.write("%-65s   %7.2f  %6.2f  %6.2f  %s   %7.1f  %7.1f  %12.6f  %10.2f  %8.2f  (%d)\n"
                     % (cand, c.dm, c.sigma, c.sigma, "%2d".center(7) % c.numharm, c.power,
