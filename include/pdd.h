@@ -834,6 +834,45 @@ int pdd_psrfits_block(const uint8_t* rows, int64_t nsub, int64_t row_bytes, int6
                       int64_t nchan, int npol, int pol0, int npol_sum, int64_t s0, int64_t n,
                       int out_code, void* out, int64_t ld_out, void* stream);
 
+/* ---- Injection of synthetic pulsars and bursts into a raw time-major block
+ * (pypulsar_amd/inject.py builds the job tables; restated in
+ * tests/inject_oracle.py).  In place on data [n][C] (rows ld
+ * elements apart, PDD_U8 or PDD_F32) whose row 0 is absolute sample t0.  With
+ * G = ceil(C / PDD_INJECT_GROUP), job j < J and channel c < C:
+ *   phase  uint64  [J][C][2]      P0, step: the phase at sample 0 and per
+ *                                 sample, in units of 2^-64 turns
+ *   drift  float64 [J][C][2]      k2 (per channel), k3 (the job's, repeated)
+ *   range  int64   [J][C + G][2]  lo, hi: the job touches samples lo <= i < hi
+ *                                 of channel c; entry C + g: an interval that
+ *                                 holds those of channels 256 g .. 256 g + 255
+ *                                 (tiles it misses are skipped)
+ *   tables float32 [J][C][B + 1]  the profile at phases b / B; entry B is the
+ *                                 one read beyond the last (entry 0 again for
+ *                                 a periodic job, 0 for a burst)
+ * The cell of absolute sample i = t0 + row and channel c gets, from every job
+ * with lo <= i < hi, in job order,
+ *   p   = P0 + i step (wrapping) + U(x x (k2 + x k3)),  x = (double) i,
+ *         U(d) = (uint64)((d - floor(d)) 2^64), a difference of 1.0 counting
+ *         as 0; every operation one IEEE operation in this order
+ *   b   = p >> (64 - log2 B),  w = float((p >> (40 - log2 B)) & 0xffffff) 2^-24
+ *   acc = acc + (T[b] + (T[b + 1] - T[b]) w)            (float32, from 0)
+ * and becomes x + acc (PDD_F32) or min(vmax, max(0, floor((float(x) + acc) +
+ * u))) (PDD_U8), u = float(h >> 8) 2^-24, h = fmix(fmix(fmix(lo32(i) ^ seed) ^
+ * hi32(i) ^ 0x9e3779b9) ^ (c 0x27d4eb2f)) in 32-bit arithmetic, fmix being
+ * MurmurHash3's finaliser.  A cell no job covers keeps its value: it is
+ * not accessed, except that where four adjacent channels of a row go as one
+ * dword or 16-byte access an uncovered cell beside a covered one is read and
+ * written back unchanged (so no other writer may own it during the call).
+ * Refused with -1, nothing touched: a null pointer (job tables: only when J >
+ * 0), another dtype, n < 0, C < 1, ld < C, t0 < 0, t0 + n > 2^52, J outside
+ * 0..PDD_INJECT_MAX_JOBS, B no power of two in 64..4096, seed outside
+ * 0..2^32 - 1, vmax outside 1..255.  n == 0 or J == 0: returns 0. */
+#define PDD_INJECT_GROUP 256
+#define PDD_INJECT_MAX_JOBS 64
+int pdd_inject(void* data, int dtype, int64_t n, int64_t C, int64_t ld, int64_t t0,
+               const uint64_t* phase, const double* drift, const int64_t* range,
+               const float* tables, int J, int B, int64_t seed, int vmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,4 +9,5 @@ there is no CPU fallback.
 """
 __version__ = "0.1.0"
 
-__all__ = ["formats", "utils", "delays", "sweep", "zero_dm", "zap", "spgroup"]
+__all__ = ["formats", "utils", "delays", "sweep", "zero_dm", "zap", "spgroup", "inject",
+           "recovery"]

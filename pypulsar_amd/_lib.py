@@ -57,7 +57,7 @@ EXPORTS = (
     "pdd_ffa_search", "pdd_sweep_execute_tm", "pdd_zap_percentile", "pdd_zap_apply",
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
     "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm", "pdd_unpack_bits",
-    "pdd_zdm_packed_int_downsample", "pdd_psrfits_block", "pdd_jerk_search",
+    "pdd_zdm_packed_int_downsample", "pdd_psrfits_block", "pdd_jerk_search", "pdd_inject",
 )
 
 
@@ -176,6 +176,8 @@ _SIGS = {
     "pdd_unpack_bits": ([_vp, _int, _i64, _i64, _i64, _vp, _i64, _vp], _int),
     "pdd_zdm_packed_int_downsample": ([_vp, _int, _i64, _i64, _i64, _i64, _int, _int, _vp, _i64,
                                        _vp], _int),
+    "pdd_inject": ([_vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _int, _i64, _int,
+                    _vp], _int),
 }
 
 

@@ -39,6 +39,13 @@ the ``.singlepulse`` file is the same with or without it.
 the raw file (masked when a mask is in use; the zero-DM filter is not
 applied), go to ``<out base>_cutouts.npz``; the ``.singlepulse`` and
 ``.spgroups`` files are the same with or without it.
+
+``--inject SPEC.json``: the synthetic bursts and pulsars of the spec
+(pypulsar_amd.inject) are added to every raw block on the device, before any
+mask; ``--recovery`` matches the candidates to them
+(pypulsar_amd.recovery) into ``<out base>_recovery.json``.  Not with
+``--cutouts``, which reads the file again: write an injected copy with
+``python -m pypulsar_amd.bin.inject`` first.
 """
 import optparse
 import os
@@ -111,9 +118,11 @@ def get_mask(infile, fb, maskfile=None, rfifind=None, block=1 << 18, file_kw=Non
 
 def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=6.0,
                 widths=None, detrendlen=1024, debug=False, maskfile=None, rfifind=None,
-                rfimask=None, file_kw=None):
+                rfimask=None, file_kw=None, injector=None):
     """``rfimask``: a mask already made (else ``maskfile`` / ``rfifind``);
-    ``file_kw``: open_search_file's keywords (PSRFITS input)."""
+    ``file_kw``: open_search_file's keywords (PSRFITS input); ``injector``: a
+    ``pypulsar_amd.inject.Injector`` whose signals are added to every raw
+    block on the device, before the mask."""
     import torch
     from pypulsar_amd.formats.psrfits import open_search_file
     from pypulsar_amd.search import DEFAULT_WIDTHS, StreamingSearch, merge
@@ -127,7 +136,8 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
                          widths=widths or DEFAULT_WIDTHS, detrendlen=detrendlen,
                          nbits=fb.nbits if fb.packed else 8, rfimask=rfimask if rfimask is not None else
                          get_mask(infile, fb, maskfile, rfifind, block, file_kw),
-                         decoder=fb.decoder() if hasattr(fb, "decoder") else None)
+                         decoder=fb.decoder() if hasattr(fb, "decoder") else None,
+                         injector=injector)
     parts = []  # candidate times are relative to the file start
     for i, c in enumerate(ss(_chunks(fb, block))):
         parts.append(c)
@@ -138,6 +148,44 @@ def search_file(infile, dms, downsamp=2, block=1 << 18, zero_dm=True, threshold=
     ss.close()
     fb.close()
     return merge(parts)
+
+
+INJECT_HINT = ("write an injected copy with `python -m pypulsar_amd.bin.inject --spec SPEC.json "
+               "-o OUT.fil INFILE` and run on that")
+
+
+def add_inject_options(parser):
+    parser.add_option("--inject", type="string", default=None, metavar="SPEC.json",
+                      help="Add the synthetic pulsars and bursts of SPEC.json (a list of "
+                           "signals, each with amp or snr; pypulsar_amd.inject) to the data on "
+                           "the device, before any mask.  snr is scaled by 1.4826 MAD per "
+                           "channel of the file's first 65536 spectra.")
+    parser.add_option("--recovery", action="store_true", default=False,
+                      help="With --inject: match the candidates to the injected signals and "
+                           "write <out base>_recovery.json.")
+
+
+def load_injector(spec, infile, file_kw=None, error=None):
+    """The Injector of --inject SPEC.json for ``infile`` (None without).  A
+    spec or a file that cannot be injected (16-bit data, ``snr`` against a
+    noise level of 0) is a ValueError, handed to ``error`` (a parser's) if
+    given."""
+    if not spec:
+        return None
+    from pypulsar_amd.formats.psrfits import open_search_file
+    from pypulsar_amd.inject import injector_for_file
+    fb = open_search_file(infile, **(file_kw or {}))
+    try:
+        if np.dtype(fb.dtype) == np.uint16:
+            raise ValueError("--inject: 16-bit data cannot be injected; convert the file to 8 or "
+                             "32 bits first")
+        return injector_for_file(spec, fb)
+    except ValueError as e:
+        if error is None:
+            raise
+        error(str(e))
+    finally:
+        fb.close()
 
 
 def file_options(options):
@@ -200,6 +248,7 @@ def main(argv=None):
     parser.add_option("--cutout-dm-half", type="float", default=None, metavar="DM",
                       help="Half-range of the DM-time image's trial DMs. (Default: the "
                            "candidate's DM, at least 10)")
+    add_inject_options(parser)
     parser.add_option("--noscales", dest="apply_scales", action="store_false", default=True,
                       help="PSRFITS input: do not apply DAT_SCL.")
     parser.add_option("--nooffsets", dest="apply_offsets", action="store_false", default=True,
@@ -219,6 +268,12 @@ def main(argv=None):
     dms = np.linspace(options.lodm, options.hidm, options.numdms)
     if options.cutouts < 0:
         parser.error("--cutouts expects a count")
+    if options.inject and options.cutouts:
+        parser.error("--inject cannot be combined with --cutouts: the cut-outs read the file "
+                     "again and would not see the signal; " + INJECT_HINT)
+    if options.recovery and not options.inject:
+        parser.error("--recovery needs --inject SPEC.json")
+    injector = load_injector(options.inject, args[0], file_kw, parser.error)
     mask = None
     if options.cutouts and (options.maskfile or options.rfifind):
         # (made once: the search and the cut-outs see the same masked data)
@@ -229,10 +284,19 @@ def main(argv=None):
     cands = search_file(args[0], dms, options.downsamp, options.block, options.zero_dm,
                         options.threshold, widths, debug=options.debug,
                         maskfile=options.maskfile, rfifind=options.rfifind, rfimask=mask,
-                        file_kw=file_kw)
+                        file_kw=file_kw, injector=injector)
     out = options.outname or os.path.splitext(args[0])[0] + ".singlepulse"
     write_singlepulse(cands, out)
     print("%d candidates -> %s" % (len(cands), out))
+    if options.recovery:
+        from pypulsar_amd import recovery
+        truth = injector.truth()
+        rep = recovery.match_bursts(truth, cands, dms, injector.freqs, injector.dt,
+                                    options.downsamp)
+        rout = os.path.splitext(out)[0] + "_recovery.json"
+        recovery.write_report(rout, truth, rep)
+        print("%d of %d injected bursts recovered -> %s"
+              % (sum(r["found"] for r in rep), len(rep), rout))
     if options.group or options.cutouts:
         from pypulsar_amd.spgroup import SinglePulseGrouper, select, write_groups
         # (the merged list is grouped once; its rows are those of the DM grid)

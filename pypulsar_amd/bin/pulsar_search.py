@@ -68,7 +68,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
                 nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2, maskfile=None,
                 rfifind=None, zaplist=None, autozap=None, file_kw=None, wmax=0, dw=20,
-                jerk_workspace_bytes=None):
+                jerk_workspace_bytes=None, injector=None):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
     pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
@@ -85,7 +85,10 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     one, run on the swept plane; its list is left as <base>.zaplist): the
     Fourier bins of those intervals are set to the whitened mean level in
     every DM row before the search; both: the two lists merged.
-    ``file_kw``: open_search_file's keywords (PSRFITS input)."""
+    ``file_kw``: open_search_file's keywords (PSRFITS input).
+    ``injector``: a ``pypulsar_amd.inject.Injector`` whose signals are added
+    to the raw block (at sample 0, before the mask; a packed file's values
+    clipped to its bit depth)."""
     import torch
     from pypulsar_amd.formats.psrfits import open_search_file
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
@@ -110,6 +113,8 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
         raw = unpack_bits(torch.from_numpy(host).cuda(), fb.nbits, C)
     else:
         raw = torch.from_numpy(fb.read_all_samples()[:n * C].reshape(n, C)).cuda()
+    if injector is not None:
+        injector.apply(raw, 0, vmax=(1 << fb.nbits) - 1 if fb.packed else None)
     if rfifind or maskfile:
         from pypulsar_amd import rfi
         if rfifind:
@@ -275,11 +280,19 @@ def main(argv=None):
                            "polarisation, AA + BB of AABB data, I of IQUV)")
     parser.add_option("-o", "--outname", default=None,
                       help="Output .accelcands file (default: INFILE with .accelcands).")
+    from pypulsar_amd.bin.frb_search import (INJECT_HINT, add_inject_options, file_options,
+                                             load_injector)
+    add_inject_options(parser)
     options, args = parser.parse_args(argv)
     if len(args) != 1:
         parser.error("one input file expected")
-    from pypulsar_amd.bin.frb_search import file_options
     options.file_kw = file_options(options)
+    if options.inject and options.fold_subbands:
+        parser.error("--inject cannot be combined with --fold-subbands: the subband fold reads "
+                     "the file again and would not see the signal; " + INJECT_HINT)
+    if options.recovery and not options.inject:
+        parser.error("--recovery needs --inject SPEC.json")
+    injector = load_injector(options.inject, args[0], options.file_kw, parser.error)
     from pypulsar_amd.periodicity import sift, write_accelcands
     if options.zmax < 0 or options.dz < 1:
         parser.error("--zmax must be >= 0 and --dz >= 1")
@@ -306,7 +319,7 @@ def main(argv=None):
                       zaplist=options.zaplist, autozap=finder, file_kw=options.file_kw,
                       wmax=options.wmax, dw=options.dw,
                       jerk_workspace_bytes=None if options.jerk_workspace_gib is None
-                      else int(options.jerk_workspace_gib * (1 << 30)))
+                      else int(options.jerk_workspace_gib * (1 << 30)), injector=injector)
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]
@@ -314,6 +327,16 @@ def main(argv=None):
     write_accelcands(sifted, out, basename=os.path.basename(base), zmax=options.zmax,
                      wmax=options.wmax)
     print("%d candidates (%d sifted) -> %s" % (len(cands), len(sifted), out))
+    if options.recovery:
+        from pypulsar_amd import recovery
+        truth = injector.truth()
+        n_plane = injector.n_samples // options.downsamp
+        rep = recovery.match_pulsars(truth, cands, n_plane * res[1], dms, injector.freqs,
+                                     injector.dt)
+        rout = os.path.splitext(out)[0] + "_recovery.json"
+        recovery.write_report(rout, truth, rep)
+        print("%d of %d injected pulsars recovered -> %s"
+              % (sum(r["found"] for r in rep), len(rep), rout))
     to_fold = sifted[:options.fold]
     if options.wmax > 0:
         jout = os.path.splitext(out)[0] + "_jerkcands.npz"

@@ -132,11 +132,14 @@ class StreamingSearch(object):
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm=True, dtype=None,
                  threshold=6.0, widths=DEFAULT_WIDTHS, detrendlen=1024, max_cands=1 << 20,
-                 rfimask=None, nbits=8, decoder=None):
+                 rfimask=None, nbits=8, decoder=None, injector=None):
         from .stream import StreamingSweep
         kw = {} if dtype is None else {"dtype": dtype}
         if rfimask is not None:
             kw["rfimask"] = rfimask
+        if injector is not None:
+            # synthetic signals added to every raw block (StreamingSweep)
+            kw["injector"] = injector
         if nbits != 8:
             # chunks are packed rows, uint8 [n, C*nbits/8] (StreamingSweep)
             kw["nbits"] = nbits

@@ -41,6 +41,8 @@ file order, 8/16-bit or float32):
     copy stream : pinned chunk i --H2D--> raw[i % 3][0:ov]      (head, event)
                   pinned chunk i --H2D--> raw[i % 3][ov:n]     (rest, event)
     compute     : raw[(i-1) % 3][block : block + ov] <- raw[i % 3][0 : ov]   (D2D)
+                  [injector.apply(raw[(i-1) % 3]): synthetic signals added, in place;
+                   chunk i's head is still untouched when it is copied above]
                   [rfimask.apply(raw[(i-1) % 3]): masked cells <- fill, in place]
                   prologue(raw[(i-1) % 3])  -> [C, (block + ov)/ds] u16 (or f32)
                   DMSweep (interleave + sweep, trim)   -> plane [D, block/ds]
@@ -112,7 +114,8 @@ class StreamingSweep(object):
     (downsampled time index)."""
 
     def __init__(self, dms, freqs, dt, block=1 << 18, downsamp=2, zero_dm="auto",
-                 dtype=torch.uint8, device="cuda", rfimask=None, nbits=8, decoder=None):
+                 dtype=torch.uint8, device="cuda", rfimask=None, nbits=8, decoder=None,
+                 injector=None):
         _lib.require_gpu()
         # decoder: a formats.psrfits.PsrfitsDecoder -- chunks are the file's
         # own SUBINT rows (pinned uint8 [k, row_bytes]), decoded on the device
@@ -134,6 +137,17 @@ class StreamingSweep(object):
         if rfimask is not None:
             assert rfimask.nchan == len(freqs), "the mask's channels are not the stream's"
             assert dtype in (torch.uint8, torch.float32), "a mask needs 8-bit or float32 input"
+        # injector: a pypulsar_amd.inject.Injector applied in place to every
+        # raw block (at its absolute start sample) before the mask -- a mask
+        # must also excise an injected signal.  Its values depend on (sample,
+        # channel) alone, and the overlap rows of a block are copied from the
+        # next chunk's head before that chunk is injected, so a row holds the
+        # same values in both blocks.  Packed input is unpacked first (never
+        # the fused prologue) and clipped to 2^nbits - 1.
+        self.injector = injector
+        if injector is not None:
+            assert injector.C == len(freqs), "the injector's channels are not the stream's"
+            assert dtype in (torch.uint8, torch.float32), "injection needs 8-bit or float32 input"
         assert block % downsamp == 0 and 64 % downsamp == 0
         self.freqs = np.asarray(freqs, dtype=np.float64)
         self.C = len(self.freqs)
@@ -152,7 +166,8 @@ class StreamingSweep(object):
             # that path does not apply): co-added values for "none", offset
             # ds vmax + co-added (x - round(mean)) for "int", co-added bytes
             # of the uint8 wrap for "wrap"
-            if not self.packed or rfimask is not None or self.row_bytes % 16:
+            if (not self.packed or rfimask is not None or injector is not None
+                    or self.row_bytes % 16):
                 return None
             return {"none": vmax, "int": 2 * vmax, "wrap": 255}.get(m, 1 << 20) * self.ds
 
@@ -237,10 +252,13 @@ class StreamingSweep(object):
 
     def _process(self, raw, n_valid, out=None, s0=0):
         """zero-DM + downsample + sweep of raw[:n_valid] -> plane (trim=True);
-        s0: the block's first input sample (for the RFI mask)."""
+        s0: the block's first input sample (for the injector and the RFI mask)."""
         if self.unpacked is not None:
             unpack_bits(raw, self.nbits, self.C, self.unpacked, n_valid)
             raw = self.unpacked
+        if self.injector is not None:
+            self.injector.apply(raw[:n_valid], s0,
+                                vmax=(1 << self.nbits) - 1 if self.packed else None)
         if self.rfimask is not None:
             self.rfimask.apply(raw[:n_valid], s0)
         nd = n_valid // self.ds
