@@ -873,6 +873,39 @@ int pdd_inject(void* data, int dtype, int64_t n, int64_t C, int64_t ld, int64_t 
                const uint64_t* phase, const double* drift, const int64_t* range,
                const float* tables, int J, int B, int64_t seed, int vmax, void* stream);
 
+/* ---- sideband search for binaries shorter than the observation
+ * (pypulsar_amd/sideband.py; Ransom, Cordes & Eikenberry 2003; restated in
+ * tests/sideband_oracle.py).  powers: whitened powers of pdd_ps_normalise,
+ * [D][nn] float32 with row stride ld; rlo as for pdd_ps_search. */
+/* One mini-FFT length L = 2^log2L (5..14) a call.  stride = L >> shift (shift
+ * 0..3); where nn - rlo >= L a row has nseg = (nn - rlo - L) / stride + 1
+ * segments, segment j starting at lo = rlo + j stride (the fewer than stride
+ * bins left below nn are not searched), otherwise none.  Of every segment,
+ * with x_i = min(P[lo + i], clip) (clip > 0; clip == 0: x_i = P[lo + i]) and
+ * A_k = sum_i x_i exp(-2 pi i i k / L), k = 0..L/2, in float32:
+ *   M[2k]     = L |A_k|^2 / A_0^2
+ *   M[2k + 1] = (pi^2 / 16) L |A_k - A_{k+1}|^2 / A_0^2
+ * for k < L/2 (the half-bin grid q = 0..L-1; a segment with A_0 <= 0, a dead
+ * row, has M = 0), and for the stages harms (HOST array, ascending, 1..8, at
+ * most 4; thr: HOST array, one float threshold per stage)
+ *   S_H[q] = sum_{h=1..H} M[h q],  q < L / H   (float32, ascending h).
+ * q of [qlo, L / H) is a candidate of stage H when S_H[q] >= thr, S_H[q] >
+ * S_H[q-1] and S_H[q] >= S_H[q+1] (neighbours outside the range: -inf); 1 <=
+ * qlo <= L / 8.  twiddle: DEVICE float32 [L/2][2] = (cos, sin)(2 pi j / L),
+ * 8-byte aligned (sideband.twiddle_table: float64, rounded once).  mini: null,
+ * or DEVICE [D][nseg][L] float32 that receives M (the same bits on every
+ * launch).  Records int32[6] {row, log2L, lo, q, H, float-bits S_H[q]} are
+ * appended, in no particular order, through the device counter *count exactly
+ * as by pdd_ps_search (always incremented, stored while < max_cands: the
+ * caller checks for overflow).  No column >= nn of a row is read.  Refused
+ * with -1, nothing launched: a null pointer, ld < nn, rlo < 1, log2L, shift,
+ * nharm, harms or qlo outside their ranges, clip < 0.  D == 0 or nseg == 0:
+ * returns 0. */
+int pdd_sb_search(const float* powers, int64_t D, int64_t nn, int64_t ld, int64_t rlo, int log2L,
+                  int shift, float clip, const int32_t* harms, int nharm, const float* thr,
+                  int qlo, const float* twiddle, float* mini, int32_t* cands, int64_t max_cands,
+                  int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,10 +210,11 @@ class AccelSearch(object):
         volume (4 nz) -- within the periodicity search's WORKSPACE_BYTES."""
         return max(1, _per.WORKSPACE_BYTES // ((24 + 4 * self.nz) * int(nfft)))
 
-    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None):
+    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None, tap=None):
         """``zap``: a ``pypulsar_amd.zap.Zaplist`` whose bins of the whitened
         spectrum are set to the whitened mean level in every row before the
-        correlation (None: nothing is zapped)."""
+        correlation (None: nothing is zapped).  ``tap``: as for
+        ``PeriodicitySearch``."""
         dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
         D, n = plane.shape
         assert len(dms) == D, "one DM per plane row"
@@ -230,6 +231,8 @@ class AccelSearch(object):
             del spec
             if zap is not None:
                 _zap.apply(wpow, zbins, white)
+            if tap is not None:
+                tap(wpow, r0, nfft)
             del wpow
             powers = self.correlate(white, n)
             c, k = self.raw(powers, nfft, dt)

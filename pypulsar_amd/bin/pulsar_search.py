@@ -41,7 +41,12 @@ the decode applies (ignored, with a note, for a filterbank).  With
 Fourier bins of periodic interference -- listed in a PRESTO ``.zaplist``, or
 found on the plane as the bins that stand out in (nearly) every DM row
 (pypulsar_amd.zap) -- are set to the whitened mean level before the
-periodicity or acceleration search.
+periodicity or acceleration search.  With ``--sideband`` the same whitened,
+zapped powers are also searched for the sideband combs of pulsars in binaries
+shorter than the observation (pypulsar_amd.sideband: short FFTs of the power
+spectrum); its sifted candidates -- orbital period and the frequency range that
+holds the spin frequency -- go to ``<base>.bincands`` and
+``<base>_bincands.npz``.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
@@ -50,6 +55,9 @@ periodicity or acceleration search.
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --fold 3 --fold-subbands 32 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 --wmax 100 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --sideband obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 --sideband --sb-maxfft 4096 \\
+        --sb-numharm 2 --sb-sigma 7 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --autozap obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zaplist site.zaplist obs.fil
@@ -68,7 +76,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, flo=1.0,
                 nfft=None, row_batch=None, return_plane=False, zmax=0, dz=2, maskfile=None,
                 rfifind=None, zaplist=None, autozap=None, file_kw=None, wmax=0, dw=20,
-                jerk_workspace_bytes=None, injector=None):
+                jerk_workspace_bytes=None, injector=None, sideband=None):
     """(candidate records, sample time of the searched plane); with
     ``return_plane`` also the searched [D, n] float32 device plane (for
     pypulsar_amd.fold): (candidates, sample time, plane).  ``zmax`` > 0: the
@@ -88,7 +96,14 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
     ``file_kw``: open_search_file's keywords (PSRFITS input).
     ``injector``: a ``pypulsar_amd.inject.Injector`` whose signals are added
     to the raw block (at sample 0, before the mask; a packed file's values
-    clipped to its bit depth)."""
+    clipped to its bit depth).  ``sideband``: a
+    ``pypulsar_amd.sideband.SidebandSearch``, or a dict of its options
+    (``sigma_threshold`` defaults to ``sigma``, ``flo`` to ``flo``): every
+    batch of whitened, zapped powers of the search above is also searched for
+    the sideband combs of binaries shorter than the observation -- no second
+    prep, FFT or whitening -- and its records (``sideband.CAND_DTYPE``) are
+    appended to the result: (candidates, sample time[, plane], sideband
+    candidates)."""
     import torch
     from pypulsar_amd.formats.psrfits import open_search_file
     from pypulsar_amd.periodicity import DEFAULT_HARMS, PeriodicitySearch
@@ -161,11 +176,21 @@ def search_file(infile, dms, downsamp=1, zero_dm=False, sigma=6.0, harms=None, f
                 len(b), int(np.sum(b[:, 1] - b[:, 0] + 1)), nf // 2, out))
             zl = zl.merged(found)
         kw["zap"] = zl
+    sb_parts = []
+    if sideband is not None:
+        from pypulsar_amd import sideband as _sb
+        if not isinstance(sideband, _sb.SidebandSearch):
+            opts = dict(sideband)
+            opts.setdefault("sigma_threshold", sigma)
+            opts.setdefault("flo", flo)
+            sideband = _sb.SidebandSearch(**opts)
+        kw["tap"] = sideband.tap(dms, dt, sb_parts)
     cands = ps(plane, dms, dt, row_batch=row_batch, nfft=nfft, **kw)
     sw.close()
-    if return_plane:
-        return cands, dt, plane
-    return cands, dt
+    res = (cands, dt, plane) if return_plane else (cands, dt)
+    if sideband is not None:
+        res += (_sb.merge(sb_parts),)
+    return res
 
 
 def main(argv=None):
@@ -230,6 +255,27 @@ def main(argv=None):
                       default=None, metavar="G",
                       help="Device memory in GiB that bounds a row batch of the jerk search, "
                            "whose whole volume of a row must be resident. (Default: 32)")
+    parser.add_option("--sideband", action="store_true", default=False,
+                      help="Also search the whitened powers of every DM row for the sideband "
+                           "combs of pulsars in binaries shorter than the observation (short "
+                           "FFTs of the power spectrum); writes <base>.bincands and "
+                           "<base>_bincands.npz.")
+    parser.add_option("--sb-minfft", dest="sb_minfft", type="int", default=32,
+                      help="Shortest mini FFT of --sideband (a power of two >= 32). (Default: 32)")
+    parser.add_option("--sb-maxfft", dest="sb_maxfft", type="int", default=16384,
+                      help="Longest mini FFT of --sideband (a power of two <= 16384). "
+                           "(Default: 16384)")
+    parser.add_option("--sb-numharm", dest="sb_numharm", type="choice",
+                      choices=["1", "2", "4", "8"], default="4",
+                      help="Largest number of summed harmonics of the comb's spacing (1, 2, 4 "
+                           "or 8). (Default: 4)")
+    parser.add_option("--sb-shift", dest="sb_shift", type="int", default=2,
+                      help="Segments of length L start L >> SHIFT bins apart (0..3). (Default: 2)")
+    parser.add_option("--sb-clip", dest="sb_clip", type="float", default=None,
+                      help="Whitened powers are clipped here before the mini FFTs (0: no clip). "
+                           "(Default: the single-bin threshold of --sb-sigma)")
+    parser.add_option("--sb-sigma", dest="sb_sigma", type="float", default=None,
+                      help="Single-trial threshold of --sideband in sigma. (Default: --sigma)")
     parser.add_option("--fold", type="int", default=0,
                       help="Fold the K strongest sifted candidates on the plane and refine "
                            "period, period derivative and DM; writes <base>_cand<k>.bestprof "
@@ -299,6 +345,24 @@ def main(argv=None):
     if options.wmax < 0 or options.dw < 1:
         parser.error("--wmax must be >= 0 and --dw >= 1")
     accelerated = options.zmax > 0 or options.wmax > 0
+    sideband = None
+    if options.sideband:
+        def pow2(v):
+            return v >= 1 and v & (v - 1) == 0
+        if not (pow2(options.sb_minfft) and pow2(options.sb_maxfft) and
+                32 <= options.sb_minfft <= options.sb_maxfft <= 16384):
+            parser.error("--sb-minfft and --sb-maxfft must be powers of two with 32 <= "
+                         "--sb-minfft <= --sb-maxfft <= 16384")
+        if not 0 <= options.sb_shift <= 3:
+            parser.error("--sb-shift must be in 0..3")
+        if options.sb_clip is not None and options.sb_clip < 0:
+            parser.error("--sb-clip must be >= 0")
+        sideband = dict(sigma_threshold=options.sigma if options.sb_sigma is None
+                        else options.sb_sigma,
+                        minfft=options.sb_minfft, maxfft=options.sb_maxfft,
+                        shift=options.sb_shift,
+                        harms=tuple(h for h in (1, 2, 4, 8) if h <= int(options.sb_numharm)),
+                        clip="auto" if options.sb_clip is None else options.sb_clip)
     if options.fold_subbands < 0 or (options.fold_subbands and options.fold <= 0):
         parser.error("--fold-subbands NSUB needs NSUB >= 0 and --fold K")
     numharm = min(options.numharm, 16) if accelerated else options.numharm
@@ -319,7 +383,8 @@ def main(argv=None):
                       zaplist=options.zaplist, autozap=finder, file_kw=options.file_kw,
                       wmax=options.wmax, dw=options.dw,
                       jerk_workspace_bytes=None if options.jerk_workspace_gib is None
-                      else int(options.jerk_workspace_gib * (1 << 30)), injector=injector)
+                      else int(options.jerk_workspace_gib * (1 << 30)), injector=injector,
+                      sideband=sideband)
     cands = res[0]
     sifted = sift(cands)
     base = os.path.splitext(args[0])[0]
@@ -327,6 +392,14 @@ def main(argv=None):
     write_accelcands(sifted, out, basename=os.path.basename(base), zmax=options.zmax,
                      wmax=options.wmax)
     print("%d candidates (%d sifted) -> %s" % (len(cands), len(sifted), out))
+    if sideband is not None:
+        from pypulsar_amd import sideband as _sb
+        bcands = res[-1]
+        bsifted = _sb.sift(bcands)
+        bout = os.path.splitext(out)[0] + ".bincands"
+        _sb.write_bincands(bsifted, bout)
+        _sb.write_bincands_npz(bsifted, os.path.splitext(out)[0] + "_bincands.npz")
+        print("%d sideband candidates (%d sifted) -> %s" % (len(bcands), len(bsifted), bout))
     if options.recovery:
         from pypulsar_amd import recovery
         truth = injector.truth()

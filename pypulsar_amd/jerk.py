@@ -266,8 +266,8 @@ class JerkSearch(object):
                                               self.workspace_bytes))
         return self.workspace_bytes // per
 
-    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None):
-        """``zap``: as for ``AccelSearch``."""
+    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None, tap=None):
+        """``zap``, ``tap``: as for ``AccelSearch``."""
         dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
         D, n = plane.shape
         assert len(dms) == D, "one DM per plane row"
@@ -286,6 +286,8 @@ class JerkSearch(object):
             del spec
             if zap is not None:
                 _zap.apply(wpow, zbins, white)
+            if tap is not None:
+                tap(wpow, r0, nfft)
             del wpow
             vol = self.correlate(white, n)
             c, k = self.raw(vol, nfft, dt)

@@ -291,10 +291,13 @@ class PeriodicitySearch(object):
         FFT's own work area) within WORKSPACE_BYTES."""
         return max(1, WORKSPACE_BYTES // (20 * int(nfft)))
 
-    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None):
+    def __call__(self, plane, dms, dt, row_batch=None, nfft=None, zap=None, tap=None):
         """``zap``: a ``pypulsar_amd.zap.Zaplist`` whose bins are set to the
         whitened mean level in every row before the search (None: nothing is
-        zapped)."""
+        zapped).  ``tap``: a callable ``tap(powers, row0, nfft)``
+        that is handed every batch's whitened (and zapped) powers [rows, nfft // 2]
+        before they are released -- how ``pypulsar_amd.sideband`` searches the same
+        powers without a second prep, FFT and whitening."""
         dms = np.atleast_1d(np.asarray(dms, dtype=np.float64))
         D, n = plane.shape
         assert len(dms) == D, "one DM per plane row"
@@ -312,6 +315,8 @@ class PeriodicitySearch(object):
             del spec
             if zap is not None:
                 _zap.apply(powers, zbins)
+            if tap is not None:
+                tap(powers, r0, nfft)
             c, k = self.raw(powers, nfft, dt)
             parts.append(self.collect(c, k, dms, nfft, dt, row0=r0))
             del powers, c, k
