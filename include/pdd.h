@@ -906,6 +906,53 @@ int pdd_sb_search(const float* powers, int64_t D, int64_t nn, int64_t ld, int64_
                   int qlo, const float* twiddle, float* mini, int32_t* cands, int64_t max_cands,
                   int64_t* count, void* stream);
 
+/* ---- coherent orbit demodulation (pypulsar_amd/orbit.py; the operation of the
+ * reference's bin/demodulate.py for a bank of trial orbits; restated in
+ * tests/orbit_oracle.py).  A time series row[0..n) of sampling time dt is
+ * resampled into the pulsar's frame by T Keplerian templates at once; the
+ * [T][n] result is searched and folded like a DM-time plane. */
+/* orbits: DEVICE float64 [T][5] = pb (s), x (projected semi-major axis, light
+ * seconds), e (in [0, 1)), omega (rad), t0 (time of periastron in s after
+ * sample 0; for e = 0 the ascending node).  The Roemer delay is
+ *   D(t) = x [(cos E - e) sin omega + sin E sqrt(1 - e^2) cos omega],
+ *   E - e sin E = 2 pi (t - t0) / pb
+ * (for e = omega = 0: x sin(2 pi (t - t0) / pb)), and output sample j (pulsar
+ * time j dt) is taken at the input position p_j = t_j / dt with
+ *   t_j - (D(t_j) - D(0)) = j dt,     so p_0 = 0.
+ * Templates are meant to have beta = x (2 pi / pb) / (1 - e) <= 0.1, a bound
+ * on |dD/dt| below which p is strictly increasing; orbit values are device
+ * data and are NOT checked here (pypulsar_amd.orbit validates them).  p is
+ * evaluated in float64 (Newton on Kepler's equation inside Newton on p, to
+ * well below 1e-9 samples) at the knots j = k K only, k = 0 .. nk - 1, nk = (n
+ * - 1) / K + 2, K a power of two in 1..256; for j = k K + i, 0 <= i < K:
+ *   w = (double) i / (double) K                       (exact)
+ *   p = p_k + (p_{k+1} - p_k) w                       (one IEEE float64
+ *                                                      operation each)
+ * The caller picks K so that A K^2 / 8 stays within its error budget, A = x (2
+ * pi / pb)^2 dt / ((1 - e)^3 (1 - beta)^3) bounding |d2p/dj2| (orbit.py:
+ * knot_spacing, 1e-3 samples).  The sample at p:
+ *   PDD_ORBIT_NEAREST  out = row[floor(p + 0.5)]      (the reference's
+ *                                                      drop / duplicate)
+ *   PDD_ORBIT_LINEAR   i0 = floor(p), f = (float)(p - (double) i0),
+ *                      out = a + (b - a) f in float32, a = row[i0], b = row[i0
+ *                      + 1]; where i0 == n - 1: out = row[n - 1]
+ * and in either mode a position outside [0, n - 1] (or a NaN) gives `fill`:
+ * no element outside [0, n) of the row is read.  out: DEVICE [T][n] float32,
+ * rows ld_out elements apart (elements n.. of a row are not written).  knots:
+ * null, or DEVICE float64 [T][nk] that receives the p_k; the bits of out and
+ * knots are the same on every launch, with or without the dump, and for any
+ * split of the templates over launches.  One launch serves all T templates, on
+ * a grid of ceil(n / tile) T workgroups, tile = (min(2045, 16384 / K) - 1) K
+ * output samples (at least 2044).  Refused with -1, nothing launched: a null
+ * row, orbits or out, n < 2 or n >= 2^31, T < 0, ld_out < n, dt <= 0, K no
+ * power of two in 1..256, another mode, ceil(n / tile) T >= 2^31 (the caller
+ * splits T).  T == 0: returns 0. */
+#define PDD_ORBIT_NEAREST 0
+#define PDD_ORBIT_LINEAR 1
+int pdd_orbit_resample(const float* row, int64_t n, double dt, const double* orbits, int64_t T,
+                       int K, int mode, float fill, float* out, int64_t ld_out, double* knots,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ HEADER = os.path.join(ROOT, "include", "pdd.h")
 SOURCES = ["pdd_ops.hip", "pdd_sweep.hip", "pdd_sweep_plan.hip", "pdd_search.hip", "pdd_psrfits.hip",
            "pdd_period.hip", "pdd_fold.hip", "pdd_accel.hip", "pdd_rfi.hip", "pdd_ffa.hip",
            "pdd_zap.hip", "pdd_spgroup.hip", "pdd_cutout.hip", "pdd_subfold.hip", "pdd_lowbit.hip",
-           "pdd_jerk.hip", "pdd_inject.hip", "pdd_sideband.hip"]
+           "pdd_jerk.hip", "pdd_inject.hip", "pdd_sideband.hip", "pdd_orbit.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-fno-slp-vectorize",
          "-ffp-contract=off"]
 MARKER = b"pdd-src-digest:"

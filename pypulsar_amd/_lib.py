@@ -29,6 +29,7 @@ STAT_MEAN, STAT_MEDIAN, STAT_STD, STAT_MIN, STAT_MAX = 0, 1, 2, 3, 4
 LAYOUT_TIME_MAJOR, LAYOUT_CHAN_MAJOR = 0, 1
 ENOCHAIN = -5          # pdd_subband_chain: geometry does not chain (nothing launched)
 ZDM_NONE, ZDM_INT, ZDM_WRAP = 0, 1, 2
+ORBIT_NEAREST, ORBIT_LINEAR = 0, 1
 SWEEP_FACTOR = 1       # pdd_sweep_plan_create_ex: exact factorised 8-bit sweeps allowed
 SWEEP_FACTOR_FORCE = 2  # ... and taken whenever the windows fit (tests)
 SWEEP_FACTOR_G2 = 4     # ... over groups of 2 channels only
@@ -58,7 +59,7 @@ EXPORTS = (
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
     "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm", "pdd_unpack_bits",
     "pdd_zdm_packed_int_downsample", "pdd_psrfits_block", "pdd_jerk_search", "pdd_inject",
-    "pdd_sb_search",
+    "pdd_sb_search", "pdd_orbit_resample",
 )
 
 
@@ -181,6 +182,8 @@ _SIGS = {
                     _vp], _int),
     "pdd_sb_search": ([_vp, _i64, _i64, _i64, _i64, _int, _int, ctypes.c_float, _vp, _int, _vp,
                        _int, _vp, _vp, _vp, _i64, _vp, _vp], _int),
+    "pdd_orbit_resample": ([_vp, _i64, ctypes.c_double, _vp, _i64, _int, _int, ctypes.c_float, _vp,
+                            _i64, _vp, _vp], _int),
 }
 
 

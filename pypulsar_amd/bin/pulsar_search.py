@@ -46,7 +46,14 @@ zapped powers are also searched for the sideband combs of pulsars in binaries
 shorter than the observation (pypulsar_amd.sideband: short FFTs of the power
 spectrum); its sifted candidates -- orbital period and the frequency range that
 holds the spin frequency -- go to ``<base>.bincands`` and
-``<base>_bincands.npz``.
+``<base>_bincands.npz``.  With ``--orbit-follow K`` the K strongest of them are
+followed up coherently (pypulsar_amd.orbit): the plane row of the candidate's DM
+is demodulated on the device by a bank of circular orbits that covers its
+orbital period, frequency range and every orbital phase, each demodulated row is
+searched like a DM row, and the sifted candidates -- a spin frequency with the
+orbit that collects its power -- go to ``<base>.orbcands`` and
+``<base>_orbcands.npz``; with ``--fold N`` the best of each followed candidate
+is folded from its demodulated row as ``<base>_orbcand<k>``.
 
     python -m pypulsar_amd.bin.pulsar_search --lodm 0 --hidm 100 --numdms 256 \\
         --downsamp 2 --sigma 8 -o obs.accelcands obs.fil
@@ -58,6 +65,8 @@ holds the spin frequency -- go to ``<base>.bincands`` and
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --sideband obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zmax 50 --sideband --sb-maxfft 4096 \\
         --sb-numharm 2 --sb-sigma 7 obs.fil
+    python -m pypulsar_amd.bin.pulsar_search --numdms 256 --numharm 2 --sideband --orbit-follow 3 \\
+        --fold 1 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --rfifind 2.0 obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --autozap obs.fil
     python -m pypulsar_amd.bin.pulsar_search --numdms 256 --zaplist site.zaplist obs.fil
@@ -276,6 +285,28 @@ def main(argv=None):
                            "(Default: the single-bin threshold of --sb-sigma)")
     parser.add_option("--sb-sigma", dest="sb_sigma", type="float", default=None,
                       help="Single-trial threshold of --sideband in sigma. (Default: --sigma)")
+    parser.add_option("--orbit-follow", dest="orbit_follow", type="int", default=0, metavar="K",
+                      help="Follow the K strongest sifted candidates of --sideband up with a "
+                           "coherent search over a bank of circular orbits: writes "
+                           "<base>.orbcands and <base>_orbcands.npz (and, with --fold, "
+                           "<base>_orbcand<k>.bestprof and .npz of the demodulated row). "
+                           "(Default: 0, off)")
+    parser.add_option("--orbit-mismatch", dest="orbit_mismatch", type="float", default=0.05,
+                      help="Largest Roemer-delay error between neighbouring templates as a "
+                           "fraction of the shortest searched period. (Default: 0.05)")
+    parser.add_option("--orbit-xmax", dest="orbit_xmax", type="float", default=None,
+                      help="Largest projected semi-major axis of the bank in light-seconds. "
+                           "(Default: what lets the comb fit the candidate's frequency range)")
+    parser.add_option("--orbit-max-templates", dest="orbit_max_templates", type="int",
+                      default=1 << 20,
+                      help="A candidate whose bank would be larger is reported and skipped. "
+                           "(Default: 1048576)")
+    parser.add_option("--orbit-mode", dest="orbit_mode", type="choice",
+                      choices=["nearest", "linear"], default="nearest",
+                      help="How the demodulated rows are sampled: the nearest sample (drop / "
+                           "duplicate) or a linear interpolation. (Default: nearest)")
+    parser.add_option("--orbit-sigma", dest="orbit_sigma", type="float", default=None,
+                      help="Single-trial threshold of --orbit-follow in sigma. (Default: --sigma)")
     parser.add_option("--fold", type="int", default=0,
                       help="Fold the K strongest sifted candidates on the plane and refine "
                            "period, period derivative and DM; writes <base>_cand<k>.bestprof "
@@ -363,6 +394,11 @@ def main(argv=None):
                         shift=options.sb_shift,
                         harms=tuple(h for h in (1, 2, 4, 8) if h <= int(options.sb_numharm)),
                         clip="auto" if options.sb_clip is None else options.sb_clip)
+    if options.orbit_follow < 0 or (options.orbit_follow and not options.sideband):
+        parser.error("--orbit-follow K needs K >= 0 and --sideband")
+    if options.orbit_mismatch <= 0 or options.orbit_max_templates < 1 or \
+            (options.orbit_xmax is not None and options.orbit_xmax <= 0):
+        parser.error("--orbit-mismatch, --orbit-xmax and --orbit-max-templates must be > 0")
     if options.fold_subbands < 0 or (options.fold_subbands and options.fold <= 0):
         parser.error("--fold-subbands NSUB needs NSUB >= 0 and --fold K")
     numharm = min(options.numharm, 16) if accelerated else options.numharm
@@ -377,7 +413,8 @@ def main(argv=None):
                               options.autozap_nsig)
     res = search_file(args[0], dms, options.downsamp, options.zero_dm, options.sigma, harms,
                       options.flo, options.nfft, options.row_batch,
-                      return_plane=options.fold > 0 or options.ffa, zmax=options.zmax,
+                      return_plane=options.fold > 0 or options.ffa or options.orbit_follow > 0,
+                      zmax=options.zmax,
                       dz=options.dz,
                       maskfile=options.maskfile, rfifind=options.rfifind,
                       zaplist=options.zaplist, autozap=finder, file_kw=options.file_kw,
@@ -400,6 +437,9 @@ def main(argv=None):
         _sb.write_bincands(bsifted, bout)
         _sb.write_bincands_npz(bsifted, os.path.splitext(out)[0] + "_bincands.npz")
         print("%d sideband candidates (%d sifted) -> %s" % (len(bcands), len(bsifted), bout))
+        if options.orbit_follow > 0:
+            follow_orbits(res[2], dms, res[1], bsifted[:options.orbit_follow],
+                          os.path.splitext(out)[0], args[0], options, max(harms))
     if options.recovery:
         from pypulsar_amd import recovery
         truth = injector.truth()
@@ -440,6 +480,73 @@ def main(argv=None):
             if options.fold_subbands:
                 fold_subbands(folded, os.path.splitext(out)[0], args[0], options, tag="ffacand")
     return 0
+
+
+def follow_orbits(plane, dms, dt, bsifted, base, infile, options, numharm):
+    """The coherent follow-up of sifted sideband candidates (``--orbit-follow``).
+    Per candidate, on the plane row of its DM: a bank of circular orbits
+    (pypulsar_amd.orbit.circular_bank) over ``porb +- porb / q`` (the half-bin
+    step of its mini spectrum), ``x <= (freq_hi - freq_lo) porb / (4 pi
+    freq_lo)`` (the comb's ``2 beta / porb`` Hz must fit the segment; or
+    ``--orbit-xmax``) and every phase; the band ``[freq_lo, freq_hi]`` of every
+    demodulated row is searched with the stages of ``--numharm`` that reach it
+    below the Nyquist frequency, and the bank's steps are set for ``f_top =
+    numharm freq_hi`` of the largest of them (at most the Nyquist frequency:
+    there is no harmonic above it).  Every demodulated row is transformed zero
+    padded to twice the FFT length of the search: once a template has put the
+    power into one bin, a spin frequency half way between two bins would lose
+    0.6 of it, while a template that leaves a residual modulation can put a
+    third of it into a sideband ``1 / porb`` away that falls on a bin -- at half
+    bins the carrier keeps at least 0.81 and wins.  A bank above
+    ``--orbit-max-templates`` is reported and skipped.  Writes ``<base>.orbcands`` and
+    ``<base>_orbcands.npz`` (the sifted candidates of all followed ones) and,
+    with ``--fold``, folds the best of each from its demodulated row
+    (``<base>_orbcand<k>.bestprof`` / ``.npz``, k the rank of the sideband
+    candidate).  Returns the sifted records."""
+    from pypulsar_amd import orbit as _orb
+    n = plane.shape[1]
+    T, nyquist = n * dt, 0.5 / dt
+    sigma = options.sigma if options.orbit_sigma is None else options.orbit_sigma
+    from pypulsar_amd.periodicity import PeriodicitySearch
+    nfft = 2 * (PeriodicitySearch.default_nfft(n) if options.nfft is None else options.nfft)
+    kept = []
+    for k, c in enumerate(bsifted, 1):
+        porb, f_lo, f_hi = float(c["porb"]), float(c["freq_lo"]), float(c["freq_hi"])
+        stages = tuple(h for h in (1, 2, 4, 8, 16, 32) if h <= numharm and h * f_lo < nyquist) \
+            or (1,)
+        x_max = options.orbit_xmax if options.orbit_xmax is not None \
+            else (f_hi - f_lo) * porb / (4.0 * np.pi * f_lo)
+        try:
+            bank = _orb.validate(_orb.circular_bank(porb - porb / float(c["q"]), porb + porb / float(c["q"]),
+                                      x_max, min(max(stages) * f_hi, nyquist), T,
+                                      options.orbit_mismatch, options.orbit_max_templates))
+        except ValueError as e:
+            print("orbit follow-up %d (DM %.2f, porb %.5f s) skipped: %s" % (k, c["DM"], porb, e))
+            continue
+        row = plane[int(c["row"])]
+        search = _orb.OrbitSearch(sigma, stages, options.orbit_mode, flo=f_lo, fhi=f_hi)
+        s = _orb.sift(search(row, float(c["DM"]), dt, bank, nfft=nfft,
+                             plane_row=int(c["row"])), ntemplates=len(bank))
+        kept.append(s)
+        if not len(s):
+            print("orbit follow-up %d (DM %.2f, porb %.5f s): %d templates, no candidate"
+                  % (k, c["DM"], porb, len(bank)))
+            continue
+        b = s[0]
+        print("orbit follow-up %d (DM %.2f, porb %.5f s): %d templates, best sigma %.2f  "
+              "f %.6f Hz  pb %.5f s  x %.6f lt-s  t0 %.5f s  (%d sifted)"
+              % (k, c["DM"], porb, len(bank), b["sigma"], b["freq"], b["pb"], b["x"], b["t0"],
+                 len(s)))
+        if options.fold > 0:
+            demod = _orb.demodulated(row, [b[name] for name in ("pb", "x", "e", "omega", "t0")], dt)
+            fold_candidates(demod[None, :], [float(c["DM"])], dt, [(0, float(b["freq"]))], base,
+                            infile, options.fold_npart, options.fold_nbins, 0, tag="orbcand",
+                            first=k)
+    sifted = np.concatenate(kept) if kept else np.empty(0, dtype=_orb.SIFTED_DTYPE)
+    _orb.write_orbcands(sifted, base + ".orbcands")
+    _orb.write_orbcands_npz(sifted, base + "_orbcands.npz")
+    print("%d orbit candidates -> %s" % (len(sifted), base + ".orbcands"))
+    return sifted
 
 
 def write_jerkcands(sifted, fn):
@@ -504,14 +611,15 @@ def fold_subbands(folded, base, infile, options, tag="cand"):
 
 
 def fold_candidates(plane, dms, dt, sifted, base, infile, npart=32, nbins=64, dm_halfwidth=2,
-                    tag="cand"):
+                    tag="cand", first=1):
     """Fold sifted candidates on the plane; writes ``<base>_<tag><k>.bestprof``
     and ``<base>_<tag><k>.npz`` (k from 1, by descending sigma; ``tag``:
-    ``cand``, or ``ffacand`` for those of the fast-folding search) and prints
-    one line per candidate.  Returns the FoldedCandidates."""
+    ``cand``, or ``ffacand`` for those of the fast-folding search; ``first``:
+    the k of the first one) and prints one line per candidate.  Returns the
+    FoldedCandidates."""
     from pypulsar_amd.fold import Folder, write_bestprof
     folded = Folder(npart, nbins)(plane, dms, dt, sifted, dm_halfwidth=dm_halfwidth)
-    for k, fc in enumerate(folded, 1):
+    for k, fc in enumerate(folded, first):
         name = "%s_%s%d" % (base, tag, k)
         write_bestprof(fc, name + ".bestprof", infile=infile, candname=os.path.basename(name))
         np.savez(name + ".npz", subints=fc.subints, subint_counts=fc.subint_counts,
