@@ -873,6 +873,49 @@ int pdd_inject(void* data, int dtype, int64_t n, int64_t C, int64_t ld, int64_t 
                const uint64_t* phase, const double* drift, const int64_t* range,
                const float* tables, int J, int B, int64_t seed, int vmax, void* stream);
 
+/* pdd_inject with pulsars in Keplerian orbits (pypulsar_amd/inject.py builds
+ * the tables; restated in tests/inject_orbit_oracle.py).  The
+ * first fifteen arguments, the cell rule and the refusals are pdd_inject's.
+ * A job j with an orbit (pb, x, e, omega, t0; the elements and the Roemer
+ * delay D(t) of pdd_orbit_resample below) has the phase
+ *   Phi(t) = phi0 + f t + fd t^2 / 2 + fdd t^3 / 6 - f (D(t) - D(0)),
+ * whose last term Q = f (D - D(0)), in turns, is periodic in the orbital phase
+ * psi = (t - t0) / pb and comes from a table of one orbit:
+ *   ophase uint64  [J][C]   O0: psi of sample 0 in channel c, in units of
+ *                           2^-64 orbits (read only for jobs with an orbit)
+ *   ometa  int64   [J][3]   HOST array: m (-1: the job has no orbit and
+ *                           follows pdd_inject's rule bit for bit; else 6..22:
+ *                           its table has M + 1 = 2^m + 1 knots), ostep (psi
+ *                           per sample, in 2^-64 orbits, the uint64's bits)
+ *                           and the byte offset of the job's table in qtab
+ *   qtab   float64 [qlen]   DEVICE, 8-byte aligned: per such job M + 1 knots
+ *                           Q(k / M), k = 0..M, knot M repeating knot 0
+ * For a job with an orbit the phase of a cell is, every operation one IEEE
+ * operation in this order,
+ *   psi = O0 + i ostep                                      (wrapping uint64)
+ *   k   = psi >> (64 - m)
+ *   w   = (double)((psi >> (32 - m)) & 0xffffffff) 2^-32    (exact)
+ *   q   = qtab[k] + (qtab[k + 1] - qtab[k]) w               (float64)
+ *   p   = P0 + i step + U(x x (k2 + x k3)) - U(q)           (wrapping)
+ * and everything after p is pdd_inject's.  k is the top m bits of psi, so k +
+ * 1 <= M whatever ophase holds, and a table must lie inside [0, qlen): no
+ * element outside qtab[0..qlen) is read.  The orbit's values (ophase, qtab)
+ * are device data and are NOT otherwise checked (pypulsar_amd.inject validates
+ * the orbit, beta <= 0.1).  A launch in which some job has an orbit takes
+ * tiles of 32 rows (pdd_inject: 64); the bits do not depend on the tiling.
+ * With every m == -1 the call is pdd_inject's, launch included.  Refused with
+ * -1, nothing touched, before any device call: what pdd_inject refuses; a null
+ * ometa (J > 0); an m outside 6..22 and not -1; with some m >= 0: a null
+ * ophase or qtab, a qtab that is not 8-byte aligned, a table offset that is
+ * negative or no multiple of 8, a table that runs past qlen. */
+#define PDD_INJECT_ORBIT_MIN_M 6
+#define PDD_INJECT_ORBIT_MAX_M 22
+int pdd_inject_orbit(void* data, int dtype, int64_t n, int64_t C, int64_t ld, int64_t t0,
+                     const uint64_t* phase, const double* drift, const int64_t* range,
+                     const float* tables, int J, int B, int64_t seed, int vmax,
+                     const uint64_t* ophase, const int64_t* ometa, const double* qtab,
+                     int64_t qlen, void* stream);
+
 /* ---- sideband search for binaries shorter than the observation
  * (pypulsar_amd/sideband.py; Ransom, Cordes & Eikenberry 2003; restated in
  * tests/sideband_oracle.py).  powers: whitened powers of pdd_ps_normalise,

@@ -59,7 +59,7 @@ EXPORTS = (
     "pdd_spg_label", "pdd_spg_summarise", "pdd_cutout_ft", "pdd_cutout_dmt",
     "pdd_subfold_zero", "pdd_subfold", "pdd_subfold_dm", "pdd_unpack_bits",
     "pdd_zdm_packed_int_downsample", "pdd_psrfits_block", "pdd_jerk_search", "pdd_inject",
-    "pdd_sb_search", "pdd_orbit_resample",
+    "pdd_sb_search", "pdd_orbit_resample", "pdd_inject_orbit",
 )
 
 
@@ -180,6 +180,8 @@ _SIGS = {
                                        _vp], _int),
     "pdd_inject": ([_vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _int, _i64, _int,
                     _vp], _int),
+    "pdd_inject_orbit": ([_vp, _int, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _int, _i64,
+                          _int, _vp, _vp, _vp, _i64, _vp], _int),
     "pdd_sb_search": ([_vp, _i64, _i64, _i64, _i64, _int, _int, ctypes.c_float, _vp, _int, _vp,
                        _int, _vp, _vp, _vp, _i64, _vp, _vp], _int),
     "pdd_orbit_resample": ([_vp, _i64, ctypes.c_double, _vp, _i64, _int, _int, ctypes.c_float, _vp,

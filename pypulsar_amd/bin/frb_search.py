@@ -41,7 +41,7 @@ applied), go to ``<out base>_cutouts.npz``; the ``.singlepulse`` and
 ``.spgroups`` files are the same with or without it.
 
 ``--inject SPEC.json``: the synthetic bursts and pulsars of the spec
-(pypulsar_amd.inject) are added to every raw block on the device, before any
+(pypulsar_amd.inject; a pulsar may be in a Keplerian orbit) are added to every raw block on the device, before any
 mask; ``--recovery`` matches the candidates to them
 (pypulsar_amd.recovery) into ``<out base>_recovery.json``.  Not with
 ``--cutouts``, which reads the file again: write an injected copy with

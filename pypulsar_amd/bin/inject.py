@@ -7,7 +7,9 @@ bursts added on the GPU (pypulsar_amd.inject).
 SPEC.json is a list of signals (or {"signals": [...], "nbins": B, "seed":
 S}), each {"kind": "pulsar", "f", "dm", ...} or {"kind": "burst", "t", "dm",
 "width", ...} with the strength as ``amp`` (data units) or ``snr`` (matched
-S/N against 1.4826 MAD per channel of the file's first 65536 spectra).  8-bit
+S/N against 1.4826 MAD per channel of the file's first 65536 spectra); a
+pulsar with ``pb`` and ``x`` (and optionally ``e``, ``omega``, ``t0``) is in a
+Keplerian orbit, and the truth carries the orbit.  8-bit
 and 32-bit SIGPROC input gives the same bit depth out under the input's own
 header; a PSRFITS file gives a SIGPROC file of its decoded type (8-bit or
 float32).  Packed (1-, 2-, 4-bit) and 16-bit input are refused.  The truth

@@ -438,18 +438,30 @@ def main(argv=None):
         _sb.write_bincands_npz(bsifted, os.path.splitext(out)[0] + "_bincands.npz")
         print("%d sideband candidates (%d sifted) -> %s" % (len(bcands), len(bsifted), bout))
         if options.orbit_follow > 0:
-            follow_orbits(res[2], dms, res[1], bsifted[:options.orbit_follow],
-                          os.path.splitext(out)[0], args[0], options, max(harms))
+            osifted = follow_orbits(res[2], dms, res[1], bsifted[:options.orbit_follow],
+                                    os.path.splitext(out)[0], args[0], options, max(harms))
     if options.recovery:
         from pypulsar_amd import recovery
         truth = injector.truth()
         n_plane = injector.n_samples // options.downsamp
-        rep = recovery.match_pulsars(truth, cands, n_plane * res[1], dms, injector.freqs,
-                                     injector.dt)
+        T = n_plane * res[1]
+        rep = recovery.match_pulsars(truth, cands, T, dms, injector.freqs, injector.dt)
+        more = {}
+        if sideband is not None:
+            more["binaries"] = recovery.match_binaries(truth, bsifted, T, dms, injector.freqs,
+                                                       injector.dt)
+            if options.orbit_follow > 0:
+                more["orbits"] = recovery.match_orbits(truth, osifted, T, dms, injector.freqs,
+                                                       injector.dt)
         rout = os.path.splitext(out)[0] + "_recovery.json"
-        recovery.write_report(rout, truth, rep)
+        recovery.write_report(rout, truth, rep, **more)
         print("%d of %d injected pulsars recovered -> %s"
               % (sum(r["found"] for r in rep), len(rep), rout))
+        for key, what in (("binaries", "found by the sideband search"),
+                          ("orbits", "found by the orbit search")):
+            if key in more:
+                print("%d of %d injected binaries %s -> %s"
+                      % (sum(r["found"] for r in more[key]), len(more[key]), what, rout))
     to_fold = sifted[:options.fold]
     if options.wmax > 0:
         jout = os.path.splitext(out)[0] + "_jerkcands.npz"

@@ -46,6 +46,32 @@ k2_c and k3 rounded to float64.  ``phase = P0_c + i step_c`` (wrapping uint64)
 floor(d)) 2^64)`` (a difference that rounds to 1.0 counts as 0), every
 operation one IEEE operation in this order.
 
+Orbits.  A pulsar may carry a Keplerian orbit ``(pb, x, e, omega, t0)``: the
+elements, units and Roemer delay ``D(t)`` of ``pypulsar_amd.orbit`` and of
+pdd_orbit_resample (include/pdd.h); ``orbit.validate`` is applied (``beta = x
+(2 pi / pb) / (1 - e) <= 0.1``).  Its phase is
+
+    Phi(t) = phi0 + f t + fd t^2 / 2 + fdd t^3 / 6 - f (D(t) - D(0)),
+
+the cubic evaluated at the pulsar time ``t - (D(t) - D(0))`` with the cross
+terms of ``fd`` and ``fdd`` with ``D`` dropped (``fd D`` is at most ``fd x``
+turns).  With ``fd = fdd = 0`` this is exactly the map pdd_orbit_resample
+inverts (``p_0 = 0``): a row injected with an orbit and demodulated with the
+same orbit is the orbit-free pulsar.  ``Q(psi) = f (D(t0 + psi pb) - D(0))``,
+in turns, is periodic in the orbital phase ``psi = (t - t0) / pb``, so one
+orbit is tabulated -- ``qtab[k] = Q(k / M)``, k = 0..M, ``qtab[M] = qtab[0]``,
+``M = 2^m`` -- and psi is carried like the spin phase: ``O0_c = round(((dt / 2
+- delta_c - t0) / pb) 2^64) mod 2^64`` per channel and ``ostep = round((dt /
+pb) 2^64) mod 2^64`` per job, each rounded once from the exact rationals of
+the float arguments.  Per cell ``psi = O0_c + i ostep`` (wrapping), ``k = psi
+>> (64 - m)``, ``w = (double)((psi >> (32 - m)) & 0xffffffff) 2^-32`` (exact),
+``q = qtab[k] + (qtab[k + 1] - qtab[k]) w`` (float64, one IEEE operation each)
+and ``U(q)`` is taken off the phase.  ``m`` is the smallest of 6..22 with ``A /
+(8 M^2) <= 1e-6`` turns, ``A = f x (2 pi)^2 / (1 - e)^3`` a bound on ``|d2Q /
+dpsi2|`` (the analytic bound, not the table's own second differences): the
+linear interpolation stays within 1e-3 of a bin of the default 1024-bin
+table.  An orbit that would need ``m > 22`` is refused.  Bursts take no orbit.
+
 Lookup: ``b = phase >> (64 - log2 B)``, ``wgt = float32((phase >> (40 - log2
 B)) & 0xffffff) 2^-24``, ``v_j = T[b] + (T[b + 1] - T[b]) wgt`` in float32,
 ``T[B]`` being ``T[0]`` for a pulsar and 0 for a burst.  The values of the
@@ -71,8 +97,36 @@ NBINS_MIN, NBINS_MAX = 64, 4096
 GROUP = 256          # channels of one envelope entry of the device `range` array
 RANGE_MAX = 1 << 62  # "everything": the default stop of a pulsar
 FWHM_TO_SIGMA = 1.0 / (2.0 * math.sqrt(2.0 * math.log(2.0)))
+_ORBIT_KEYS = ("pb", "x", "e", "omega", "t0")
 _PULSAR_KEYS = ("f", "dm", "amp", "fd", "fdd", "phi0", "width", "profile", "spectral_index",
-                "tau", "tau_index", "ref_freq", "start", "stop")
+                "tau", "tau_index", "ref_freq", "start", "stop") + _ORBIT_KEYS
+ORBIT_MIN_M, ORBIT_MAX_M = 6, 22  # log2 of the knots of an orbit's table (include/pdd.h)
+ORBIT_BUDGET = 1e-6               # turns: the interpolation error of the orbital term
+
+
+def orbit_table_bits(f, x, e):
+    """The smallest ``m`` in 6..22 with ``f x (2 pi)^2 / (1 - e)^3 / (8 (2^m)^2)
+    <= 1e-6`` turns; ValueError when 22 does not do."""
+    A = float(f) * float(x) * (2.0 * math.pi) ** 2 / (1.0 - float(e)) ** 3
+    for m in range(ORBIT_MIN_M, ORBIT_MAX_M + 1):
+        if A / (8.0 * float(1 << m) ** 2) <= ORBIT_BUDGET:
+            return m
+    raise ValueError("orbit: f = %r Hz, x = %r lt-s, e = %r need a table of more than 2^%d knots "
+                     "for %g turns" % (float(f), float(x), float(e), ORBIT_MAX_M, ORBIT_BUDGET))
+
+
+def orbit_table(f, orb, m):
+    """float64 [2^m + 1]: ``f (D(t0 + k pb / M) - D(0))`` in turns, k = 0..M,
+    the last knot repeating the first.  ``orb``: (pb, x, e, omega, t0)."""
+    from . import orbit as _orbit  # (imports torch: only signals with an orbit need it)
+    M = 1 << int(m)
+    pb, t0 = float(orb[0]), float(orb[4])
+    t = t0 + np.arange(M, dtype=np.float64) * (pb / M)
+    D = _orbit.roemer(tuple(orb), np.concatenate([t, [0.0]]))
+    q = np.empty(M + 1, dtype=np.float64)
+    q[:M] = float(f) * (D[:M] - D[M])
+    q[M] = q[0]
+    return q
 _BURST_KEYS = ("t", "dm", "amp", "width", "spectral_index", "tau", "tau_index", "ref_freq")
 
 
@@ -80,11 +134,18 @@ class PulsarSignal(object):
     """A periodic signal: frequency ``f`` (Hz) and derivatives ``fd``, ``fdd``
     at t = 0, phase ``phi0`` (turns) at t = 0, ``width`` the FWHM in turns of a
     Gaussian ``profile`` (or ``profile`` a 1-D array: one period, any length),
-    present in the samples [start, stop)."""
+    present in the samples [start, stop).  ``pb`` (s) and ``x`` (light
+    seconds) together put it into a Keplerian orbit of eccentricity ``e``,
+    longitude of periastron ``omega`` (rad) and time of periastron ``t0`` (s
+    after sample 0; ``e = 0``: the ascending node), the elements of
+    ``pypulsar_amd.orbit``: the phase loses ``f (D(t) - D(0))`` turns (the
+    module docstring; the cross term ``fd D``, at most ``fd x`` turns, is
+    dropped)."""
     kind = "pulsar"
 
     def __init__(self, f, dm, amp, fd=0.0, fdd=0.0, phi0=0.0, width=0.05, profile="gauss",
-                 spectral_index=0.0, tau=0.0, tau_index=-4.0, ref_freq=None, start=None, stop=None):
+                 spectral_index=0.0, tau=0.0, tau_index=-4.0, ref_freq=None, start=None, stop=None,
+                 pb=None, x=None, e=None, omega=None, t0=None):
         self.f, self.dm, self.amp = float(f), float(dm), float(amp)
         self.fd, self.fdd, self.phi0 = float(fd), float(fdd), float(phi0)
         self.width = float(width)
@@ -106,8 +167,33 @@ class PulsarSignal(object):
             raise ValueError("width must be positive")
         if self.tau < 0 or not 0 <= self.start <= self.stop <= RANGE_MAX:
             raise ValueError("tau >= 0 and 0 <= start <= stop are required")
+        self.orbit, self.m, self.qtab = None, -1, None
+        if (pb is None) != (x is None):
+            raise ValueError("an orbit needs pb and x together")
+        if pb is None:
+            if not (e is None and omega is None and t0 is None):
+                raise ValueError("e, omega and t0 need an orbit (pb and x)")
+            return
+        from . import orbit as _orbit  # (imports torch: only signals with an orbit need it)
+        orb = tuple(0.0 if v is None else float(v) for v in (pb, x, e, omega, t0))
+        _orbit.validate(orb)
+        self.orbit = _orbit.Orbit(*orb)
+        self.m = orbit_table_bits(self.f, self.orbit.x, self.orbit.e)
+        self.qtab = orbit_table(self.f, self.orbit, self.m)
+        self.beta = float(_orbit.beta(orb)[0])
+        # max |dD/dt| from the table's own differences: the apparent frequency
+        # stays inside [f_lo, f_hi]
+        v = float(np.max(np.abs(np.diff(self.qtab)))) * (1 << self.m) / (self.f * self.orbit.pb)
+        self.f_lo, self.f_hi = self.f * (1.0 - v), self.f * (1.0 + v)
 
     def params(self):
+        d = self._params()
+        if self.orbit is not None:
+            d.update(self.orbit._asdict())
+            d.update(beta=self.beta, f_lo=self.f_lo, f_hi=self.f_hi)
+        return d
+
+    def _params(self):
         d = dict(kind="pulsar", f=self.f, dm=self.dm, amp=self.amp, fd=self.fd, fdd=self.fdd,
                  phi0=self.phi0, width=self.width, spectral_index=self.spectral_index,
                  tau=self.tau, tau_index=self.tau_index, ref_freq=self.ref_freq,
@@ -195,7 +281,8 @@ def profile_tables(intrinsic, scale, smear, dt_turns, tau, shift, B):
 
 
 class _Job(object):
-    __slots__ = ("signal", "tables", "P0", "step", "k2", "k3", "lo", "hi", "window", "lead", "scale")
+    __slots__ = ("signal", "tables", "P0", "step", "k2", "k3", "lo", "hi", "window", "lead", "scale",
+                 "O0", "ostep")
 
 
 class Injector(object):
@@ -244,6 +331,7 @@ class Injector(object):
         job.step = np.zeros(C, dtype=np.uint64)
         job.k2 = np.zeros(C, dtype=np.float64)
         job.k3 = 0.0
+        job.O0, job.ostep = np.zeros(C, dtype=np.uint64), 0
         if s.kind == "pulsar":
             job.window, job.lead = 1.0 / s.f, 0.0
             turn = s.f  # turns per second
@@ -254,6 +342,11 @@ class Injector(object):
                 job.P0[c], job.step[c], job.k2[c] = P0, step, k2
             job.lo = np.full(C, s.start, dtype=np.int64)
             job.hi = np.full(C, s.stop, dtype=np.int64)
+            if s.orbit is not None:
+                dtf, pbf, t0f = Fraction(dt), Fraction(s.orbit.pb), Fraction(s.orbit.t0)
+                job.ostep = round(dtf / pbf * _M64) % _M64
+                for c in range(C):
+                    job.O0[c] = round((dtf / 2 - Fraction(float(delta[c])) - t0f) / pbf * _M64) % _M64
             return job
         W, lead = burst_window(s.width, float(smear.max()), dt, float(tau.max()))
         job.window, job.lead = W, lead
@@ -310,6 +403,32 @@ class Injector(object):
                 tab[j, :, B] = tab[j, :, 0]
         return phase, drift, rng, tab
 
+    def has_orbits(self):
+        return any(getattr(j.signal, "orbit", None) is not None for j in self.jobs)
+
+    def orbit_arrays(self):
+        """The orbit tables in the layouts pdd_inject_orbit takes
+        (include/pdd.h): ophase uint64 [J, C] (O0; 0 for a job without an
+        orbit); ometa int64 [J, 3] (m, or -1: no orbit; ostep, the uint64's
+        bits; the byte offset of the job's table in qtab); qtab float64, the
+        tables of the jobs with an orbit one after the other (``2^m + 1``
+        knots each; empty when no job has an orbit)."""
+        J, C = len(self.jobs), self.C
+        ophase = np.zeros((J, C), dtype=np.uint64)
+        ometa = np.zeros((J, 3), dtype=np.int64)
+        ometa[:, 0] = -1
+        tabs, at = [], 0
+        for j, job in enumerate(self.jobs):
+            s = job.signal
+            if getattr(s, "orbit", None) is None:
+                continue
+            ophase[j] = job.O0
+            ometa[j] = (s.m, np.array(job.ostep, dtype=np.uint64).view(np.int64), 8 * at)
+            tabs.append(s.qtab)
+            at += s.qtab.size
+        qtab = np.concatenate(tabs) if tabs else np.zeros(0, dtype=np.float64)
+        return ophase, ometa, qtab
+
     def _sigma_sum(self, sigma_chan):
         s = np.broadcast_to(np.asarray(sigma_chan, dtype=np.float64), (self.C,))
         return math.sqrt(float(np.sum(s * s)))
@@ -320,7 +439,10 @@ class Injector(object):
         with E the aligned channel sum of the float64 tables, sqrt(n
         var_phi(E)) / sqrt(sum sigma_c^2) for a pulsar over n = the samples
         of [start, stop) within ``n_samples``, sqrt((W / dt) mean_phi(E^2)) /
-        sqrt(sum sigma_c^2) for a burst."""
+        sqrt(sum sigma_c^2) for a burst.  An orbit does not enter: it changes
+        the number of samples per turn by at most beta <= 0.1 (in practice
+        below 0.02) and not the energy per turn, so the figure is the
+        orbit-free pulsar's, good to that fraction."""
         noise = self._sigma_sum(sigma_chan)
         if not noise > 0:
             raise ValueError("a matched S/N needs a noise level: sigma_chan is 0 in every channel "
@@ -420,6 +542,16 @@ class Injector(object):
                               torch.from_numpy(tab).to(device))
         return self._dev[key]
 
+    def _device_orbit_arrays(self, device):
+        """(ophase, qtab) on the device, ometa on the host."""
+        import torch
+        key = "orbit:" + str(device)
+        if key not in self._dev:
+            ophase, ometa, qtab = self.orbit_arrays()
+            self._dev[key] = (torch.from_numpy(ophase.view(np.int64)).to(device),
+                              np.ascontiguousarray(ometa), torch.from_numpy(qtab).to(device))
+        return self._dev[key]
+
     def apply(self, block, t0=0, stream=None, vmax=None):
         """Add the signals, in place, to the time-major device block [n, C]
         (8-bit or float32) whose first row is sample ``t0``; returns the
@@ -436,9 +568,15 @@ class Injector(object):
         if n == 0 or not self.jobs:
             return block
         phase, drift, rng, tab = self._device_arrays(block.device)
-        call("pdd_inject", ptr(block), codes[block.dtype], n, self.C, block.stride(0), int(t0),
-             ptr(phase), ptr(drift), ptr(rng), ptr(tab), len(self.jobs), self.B, self.seed,
-             self.vmax if vmax is None else int(vmax), stream_ptr(stream))
+        args = (ptr(block), codes[block.dtype], n, self.C, block.stride(0), int(t0),
+                ptr(phase), ptr(drift), ptr(rng), ptr(tab), len(self.jobs), self.B, self.seed,
+                self.vmax if vmax is None else int(vmax))
+        if self.has_orbits():
+            ophase, ometa, qtab = self._device_orbit_arrays(block.device)
+            call("pdd_inject_orbit", *(args + (ptr(ophase), ometa.ctypes.data, ptr(qtab),
+                                               qtab.numel(), stream_ptr(stream))))
+        else:
+            call("pdd_inject", *(args + (stream_ptr(stream),)))
         return block
 
 

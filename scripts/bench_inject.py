@@ -7,6 +7,10 @@ source digest:
 * 1, 4 and 16 pulsars at B = 1024 (fd = fdd = 0: the integer phase alone),
   4 pulsars with fd and fdd (the float64 drift per cell), 1 and 64 bursts
   (B = 256 for the 64, which keeps their tables at 270 MB), an empty job list;
+* 1 and 4 pulsars in Keplerian orbits (pdd_inject_orbit), wide (pb about a
+  quarter of the block, circular, a table of 2^m + 1 knots with m about 13)
+  and tight (pb about 600 s, e = 0.9, f = 500 Hz: m = 21, a table of 16 MB
+  per pulsar);
 * beside the block-bytes floor: one read and one write of the block at the
   6.2 TB/s achievable rate DESIGN.md uses;
 * the BASELINE configs[4] stream (StreamingSweep, pinned H2D included) per
@@ -80,6 +84,20 @@ def main(argv=None):
                              fd=1e-3 if curved else 0.0, fdd=1e-6 if curved else 0.0)
                 for _ in range(k)]
 
+    def binaries(k, tight):
+        out = []
+        for i in range(k):
+            if tight:
+                orb = dict(pb=600.0 + 7.0 * i, x=0.5, e=0.9, omega=1.0, t0=100.0 + i)
+                f = 500.0 - i
+            else:
+                orb = dict(pb=T * DT / 4.0 * (1.0 + 0.1 * i), x=0.01, t0=0.3 * i)
+                f = float(rng.uniform(50, 500))
+            out.append(PulsarSignal(f=f, dm=float(rng.uniform(5, 300)),
+                                    amp=float(rng.uniform(0.05, 0.5)),
+                                    width=float(rng.uniform(0.02, 0.1)), **orb))
+        return out
+
     def bursts(k):
         return [BurstSignal(t=float(rng.uniform(0.05, 0.8)) * T * DT, dm=float(rng.uniform(20, 300)),
                             amp=float(rng.uniform(1, 20)), width=float(rng.uniform(5e-4, 4e-3)))
@@ -88,7 +106,11 @@ def main(argv=None):
     cases = [("empty job list", [], 1024), ("1 pulsar", pulsars(1), 1024),
              ("4 pulsars", pulsars(4), 1024), ("16 pulsars", pulsars(16), 1024),
              ("4 pulsars, fd and fdd", pulsars(4, True), 1024), ("1 burst", bursts(1), 1024),
-             ("64 bursts (B = 256)", bursts(64), 256)]
+             ("64 bursts (B = 256)", bursts(64), 256),
+             ("1 pulsar in a wide orbit", binaries(1, False), 1024),
+             ("4 pulsars in wide orbits", binaries(4, False), 1024),
+             ("1 pulsar in a tight orbit", binaries(1, True), 1024),
+             ("4 pulsars in tight orbits", binaries(4, True), 1024)]
     res = {}
     gen = torch.Generator(device="cuda").manual_seed(1)
     stream_inj = None
@@ -115,6 +137,9 @@ def main(argv=None):
             r.update(block_bytes_floor_ms=floor_ms, fraction_of_floor=floor_ms / r["ms"],
                      ns_per_job_cell=(1e6 * r["ms"] / r["job_cells"]) if r["job_cells"] else None,
                      nbins=B, table_bytes=len(sigs) * C * (B + 1) * 4, host_build_s=host_s)
+            if it.has_orbits():
+                r.update(orbit_m=[int(s.m) for s in sigs],
+                         orbit_table_bytes=int(it.orbit_arrays()[2].nbytes))
             res["%s, %s" % (name, tag)] = r
             print("%-30s %-3s %8.3f ms (%.3f-%.3f)  floor %.3f ms (%.3f of it)  %s ns per job cell"
                   % (name, tag, r["ms"], r["ms_min"], r["ms_max"], floor_ms, r["fraction_of_floor"],
